@@ -14,10 +14,18 @@ per-thread buffers, 1M object intervals (+ 8 globals + [stack]), 8 threads.
 Weak scaling: every rank analyses its own 125M-record shard against the same
 table, so --gpus 8 is configs[3] (1B records).  configs[1] (10M records, 1k
 intervals) and configs[2] (100M records, 100k intervals, per-page on) are measured
-after it and reported in the same JSON line under "secondary".
+after it and reported in the same JSON line under "secondary", and the CPU
+baselines under "cpu_baseline", only with --full: a plain run sets up, warms up,
+times its steps and prints the line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|k1m]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of
+the engine reads it back, to DIR/<name>.npy (float64; dump_outputs below).  The
+workload is seeded, so two builds run with the same arguments analyse the same
+bytes and their dumps compare array for array.
 """
 from __future__ import annotations
 
@@ -37,6 +45,7 @@ RECORD_BYTES = 40
 COMPACT_BYTES = 16  # partition-first path: compact record per routed sample
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 MIN_TIMED_S = 1.0      # default --steps: enough steps for at least this much timed work
+DUMP_MAX_CELLS = 500_000  # --dump-outputs: page-histogram rows kept (a seeded sample above that)
 
 WORKLOADS = {
     "c2": dict(nb_samples=10_000_000, nb_intervals=1_000, desc="configs[1]: 10M PEBS records/GPU, 1k object intervals"),
@@ -50,6 +59,16 @@ WORKLOADS = {
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def host_threads():
+    """This job's CPU share: OMP_NUM_THREADS, else every CPU."""
+    return max(1, int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1)))
+
+
+def gen_workers():
+    """Threads the generator computes the batch on (the batch is the same for every count)."""
+    return min(16, host_threads())
 
 
 class Workload:
@@ -67,12 +86,15 @@ class Workload:
         cfg_kw = {k: v for k, v in wl.items() if k != "desc"}
         self.cfg = SynthConfig(seed=1, sample_seed=1000 + rank, **cfg_kw)
         t0 = time.time()
-        self.rp = generate(self.cfg)
+        self.rp = generate(self.cfg, workers=gen_workers())
+        t1 = time.time()
         arena, offs, lens, ranks, acc = self.rp.packed()
-        log(f"[rank {rank}] {name}: {self.rp.nb_records()} records in {len(lens)} buffers, "
-            f"{arena.nbytes / 1e6:.0f} MB, generated in {time.time() - t0:.1f}s")
+        log(f"[rank {rank}] {name}: {int(lens.sum()) // RECORD_BYTES} records in {len(lens)} buffers, "
+            f"{arena.nbytes / 1e6:.0f} MB, generated in {t1 - t0:.1f}s, packed in {time.time() - t1:.1f}s")
+        t1 = time.time()
         self.d_arena = torch.from_numpy(arena).to(device)
         del arena
+        log(f"[rank {rank}] {name}: batch on the device in {time.time() - t1:.1f}s")
         self.nb_buf = len(lens)
         self.samples = int(lens.sum()) // RECORD_BYTES
         # (NMG_BENCH_DEBUG_FLAGS: internal ablation switches for counter
@@ -158,15 +180,57 @@ def timed_run(w, steps, warmup, barrier, agree=None):
     return time.perf_counter() - t_start, steps
 
 
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the counters the last timed step left in the engine, read
+    back through the getters a caller uses, one float64 array per
+    out_dir/<name>.npy (the u64 counts and weights of these workloads are far
+    below 2^53, so exact; a min that never saw a sample keeps its u64 sentinel,
+    rounded the same way in every build):
+
+      global_counters [2, 75]   struct mem_counters of reads and writes
+      nb_samples_found [2]      records decoded, records attributed to an object
+      buffer_samples, buffer_found [buffers]
+      object_first [E], object_count_weight [E, 2, 2]
+      page_cells [n, 4]         the per-page histogram's rows, sorted; above
+                                DUMP_MAX_CELLS rows a fixed seeded sample of them
+      page_cells_total [1]      n before sampling
+
+    About 58 MB at the default workload (1.03M table entries)."""
+    os.makedirs(out_dir, exist_ok=True)
+    g, ns, nf = eng.global_counters()
+    bs, bf = eng.buffer_counts()
+    first, cw = eng.object_counters()
+    cells = eng.page_cells()
+    total = cells.shape[0]
+    cells = cells[np.lexsort(cells.T[::-1])]  # (the engine's row order is not part of its contract)
+    if total > DUMP_MAX_CELLS:
+        cells = cells[np.sort(np.random.default_rng(0).choice(total, DUMP_MAX_CELLS, replace=False))]
+    out = {"global_counters": g, "nb_samples_found": np.array([ns, nf]), "buffer_samples": bs, "buffer_found": bf,
+           "object_first": first, "object_count_weight": cw, "page_cells": cells,
+           "page_cells_total": np.array([total])}
+    nbytes = 0
+    for name, a in out.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        nbytes += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert nbytes <= 64_000_000, nbytes
+    log(f"[rank 0] outputs of the last timed step: {len(out)} arrays, {nbytes / 1e6:.1f} MB in {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="timed steps (0: enough for >= 1 s)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the --secondary workloads and the CPU baselines "
+                         "(N=1); without it the run ends with the main workload's line")
     ap.add_argument("--secondary", default="c2,c3",
-                    help="workloads measured after the main one, comma-separated (N=1; '' = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: workloads measured after the main one, comma-separated (N=1; '' = none)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--handle", action="store_true",
                     help="without a launcher, drive the GPUs through one engine handle even for --gpus 1 "
                          "(host-staged buffers, as --gpus N > 1 does), so a 1 -> N curve compares one path")
@@ -177,7 +241,7 @@ def main():
     ap.add_argument("--cpu-mt-records", type=int, default=62_500_000,
                     help="records in the multi-threaded baseline's sample (about 0.8 s a run on 16 threads: long "
                          "enough that the shared host's noise averages out within a run)")
-    ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1)),
+    ap.add_argument("--cpu-threads", type=int, default=host_threads(),
                     help="host threads of the multi-threaded CPU baseline (default: this job's CPU share, "
                          "OMP_NUM_THREADS, else every CPU)")
     args = ap.parse_args()
@@ -238,6 +302,8 @@ def main():
     # sanity: every record of the batch was decoded exactly once per step
     g, ns, nf = w.eng.global_counters()
     assert ns == w.samples or os.environ.get("NMG_BENCH_DEBUG_FLAGS"), (ns, w.samples)
+    if args.dump_outputs and rank == 0:  # (rank 0's own counters, before the report's merge)
+        dump_outputs(w.eng, args.dump_outputs)
 
     if distributed:
         merge_engine(w.eng, dst=0)  # full merge once (dense + gathers) for the report
@@ -255,7 +321,7 @@ def main():
         out = result_line(args, w, world, steps, ms_per_step, value, attr_ms, total_ms, phases)
         if split:
             out["merge"] = split
-        if world == 1 and args.secondary:
+        if world == 1 and args.full and args.secondary:
             out["secondary"] = {}
             for name in args.secondary.split(","):
                 s = Workload(name, rank, device, False)
@@ -276,7 +342,7 @@ def main():
                     out["secondary"][s.name]["cpu_reference_loop"] = reference_loop_full(s.rp)
                 s.eng.close()
                 del s
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log(f"[rank 0] cpu baseline: first {args.cpu_records} records")
             out["cpu_baseline"] = cpu_baseline(w.rp, args.cpu_records, args.cpu_mt_records, args.cpu_threads,
                                          args.cpu_st_records)
@@ -309,7 +375,7 @@ def main_one_process(args):
     wl = WORKLOADS[args.workload]
     cfg = SynthConfig(seed=1, sample_seed=1000, **{k: v for k, v in wl.items() if k != "desc"})
     t0 = time.time()
-    rp = generate(cfg)
+    rp = generate(cfg, workers=gen_workers())
     bufs = [b.linear() for b in rp.buffers]
     shard = sum(x.nbytes for x in bufs) // RECORD_BYTES
     log(f"[1 process, {n} GPUs] {args.workload}: shard of {shard} records in {len(bufs)} buffers, generated in "
@@ -335,6 +401,8 @@ def main_one_process(args):
     merge_ms, payload = eng.merge_stats()  # (the last step's merge, GPU events on the root device)
     g, ns, nf = eng.global_counters()
     assert ns == n * shard, (ns, n * shard)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
     ms_per_step = elapsed * 1e3 / steps
     out = {
         "metric": "PEBS samples/s analysed (device-resident)",

@@ -39,6 +39,7 @@ from __future__ import annotations
 
 import dataclasses
 import struct
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -505,19 +506,13 @@ def make_table(cfg: SynthConfig, rng: np.random.Generator) -> ObjectTable:
     return ObjectTable(keys_all, eo, ent_all, pool_arr.astype(np.uint64), bytes(strings))
 
 
-def _records(n: int, rng: np.random.Generator, cfg: SynthConfig, table: ObjectTable,
-             heap_keys: np.ndarray, heap_first: int, zipf_cdf: np.ndarray, access: int,
-             t_lo: int, t_hi: int) -> np.ndarray:
-    rec = np.zeros(n, dtype=RECORD_DTYPE)
-    rec["type"] = PERF_RECORD_SAMPLE
-    rec["misc"] = 2  # PERF_RECORD_MISC_USER
-    rec["size"] = RECORD_BYTES
-    ts = np.sort(rng.integers(t_lo, t_hi, n, dtype=np.uint64))
-    rec["timestamp"] = ts
+def _draw_records(n: int, rng: np.random.Generator, cfg: SynthConfig, K: int, access: int,
+                  t_lo: int, t_hi: int) -> dict:
+    """Every random draw of one (thread, access) block of n records, in the
+    order of the seeded stream (which fixes the workload); what is computed
+    from the draws is left to _finish_records, which needs no generator."""
+    d = {"ts": rng.integers(t_lo, t_hi, n, dtype=np.uint64)}
     u = rng.random(n)
-    addr = np.zeros(n, dtype=np.uint64)
-    ent = table.entries
-    K = heap_keys.shape[0]
     # objects: Zipf over a random permutation of the heap keys
     cat_stack = u < cfg.frac_stack
     cat_gap = (u >= cfg.frac_stack) & (u < cfg.frac_stack + cfg.frac_gap)
@@ -525,8 +520,45 @@ def _records(n: int, rng: np.random.Generator, cfg: SynthConfig, table: ObjectTa
     cat_obj = ~(cat_stack | cat_gap | cat_glob)
     no = int(cat_obj.sum())
     if no:
-        rank = np.searchsorted(zipf_cdf, rng.random(no))
-        perm = _perm_cache(K, cfg.seed)
+        d["obj_rank"] = rng.random(no)
+        d["obj_off"] = rng.random(no)
+    ng = int(cat_glob.sum())
+    if ng and cfg.nb_globals:
+        d["glob_i"] = rng.integers(0, cfg.nb_globals, ng)
+        d["glob_off"] = rng.random(ng)
+    elif ng:
+        cat_gap |= cat_glob
+    ngap = int(cat_gap.sum())
+    if ngap:
+        d["gap_k"] = rng.integers(0, K, ngap)
+        d["gap_off"] = rng.random(ngap)
+    ns = int(cat_stack.sum())
+    if ns:
+        d["stack"] = rng.integers(0x7FFC00000000, 0x7FFF00000000, ns, dtype=np.uint64)
+    if access == 0:
+        d["weight"] = rng.normal(2.5, 1.2, n)
+    d["lvl"] = rng.random(n)
+    # upper data_src fields (snoop / lock / tlb) are noise for the analyser
+    d["noise"] = rng.integers(0, 1 << 16, n, dtype=np.uint64)
+    d.update(cat_stack=cat_stack, cat_gap=cat_gap, cat_glob=cat_glob, cat_obj=cat_obj)
+    return d
+
+
+def _finish_records(d: dict, n: int, cfg: SynthConfig, table: ObjectTable, heap_keys: np.ndarray,
+                    heap_first: int, zipf_cdf: np.ndarray, perm: np.ndarray, access: int) -> np.ndarray:
+    """The records of one block from its draws (_draw_records)."""
+    rec = np.zeros(n, dtype=RECORD_DTYPE)
+    rec["type"] = PERF_RECORD_SAMPLE
+    rec["misc"] = 2  # PERF_RECORD_MISC_USER
+    rec["size"] = RECORD_BYTES
+    ts = np.sort(d["ts"])
+    rec["timestamp"] = ts
+    addr = np.zeros(n, dtype=np.uint64)
+    ent = table.entries
+    K = heap_keys.shape[0]
+    cat_stack, cat_gap, cat_glob, cat_obj = d["cat_stack"], d["cat_gap"], d["cat_glob"], d["cat_obj"]
+    if "obj_rank" in d:
+        rank = np.searchsorted(zipf_cdf, d["obj_rank"])
         k = perm[np.minimum(rank, K - 1)]
         e0 = table.entry_off[heap_first + k].astype(np.int64)
         e1 = table.entry_off[heap_first + k + 1].astype(np.int64)
@@ -540,36 +572,29 @@ def _records(n: int, rng: np.random.Generator, cfg: SynthConfig, table: ObjectTa
             e += past.astype(np.int64)
         base = ent["buffer_addr"][e]
         sz = ent["buffer_size"][e]
-        addr[cat_obj] = base + (rng.random(no) * sz).astype(np.uint64)
-    ng = int(cat_glob.sum())
-    if ng and cfg.nb_globals:
-        gi = rng.integers(0, cfg.nb_globals, ng)
-        addr[cat_glob] = ent["buffer_addr"][gi] + (rng.random(ng) * cfg.global_size).astype(np.uint64)
-    elif ng:
-        cat_gap |= cat_glob
-    ngap = int(cat_gap.sum())
-    if ngap:
-        k = rng.integers(0, K, ngap)
+        addr[cat_obj] = base + (d["obj_off"] * sz).astype(np.uint64)
+    if "glob_i" in d:
+        addr[cat_glob] = ent["buffer_addr"][d["glob_i"]] + (d["glob_off"] * cfg.global_size).astype(np.uint64)
+    if "gap_k" in d:
+        k = d["gap_k"]
         e0 = table.entry_off[heap_first + k].astype(np.int64)
         start = heap_keys[k] + ent["initial_buffer_size"][e0]
         nxt = np.where(k + 1 < K, heap_keys[np.minimum(k + 1, K - 1)], start + np.uint64(4096))
         width = np.maximum(nxt - start, np.uint64(1))
-        addr[cat_gap] = start + (rng.random(ngap) * width).astype(np.uint64)
-    ns = int(cat_stack.sum())
-    if ns:
-        addr[cat_stack] = rng.integers(0x7FFC00000000, 0x7FFF00000000, ns, dtype=np.uint64)
+        addr[cat_gap] = start + (d["gap_off"] * width).astype(np.uint64)
+    if "stack" in d:
+        addr[cat_stack] = d["stack"]
     rec["addr"] = addr
     if access == 0:
-        w = np.clip(np.round(np.exp(rng.normal(2.5, 1.2, n))), 1, 2000).astype(np.uint64)
+        w = np.clip(np.round(np.exp(d["weight"])), 1, 2000).astype(np.uint64)
     else:
         w = np.zeros(n, dtype=np.uint64)
     rec["weight"] = w
     probs = np.array([p for _, p in _LVL_MIX])
     lv = np.array([l for l, _ in _LVL_MIX], dtype=np.uint64)
-    li = np.searchsorted(np.cumsum(probs) / probs.sum(), rng.random(n))
+    li = np.searchsorted(np.cumsum(probs) / probs.sum(), d["lvl"])
     op = MEM_OP_LOAD if access == 0 else MEM_OP_STORE
-    # upper data_src fields (snoop / lock / tlb) are noise for the analyser
-    noise = rng.integers(0, 1 << 16, n, dtype=np.uint64) << np.uint64(19)
+    noise = d["noise"] << np.uint64(19)
     rec["data_src"] = (lv[np.minimum(li, lv.shape[0] - 1)] << np.uint64(5)) | np.uint64(op) | noise
     return rec
 
@@ -585,8 +610,10 @@ def _perm_cache(K: int, seed: int) -> np.ndarray:
     return _PERM[key]
 
 
-def generate(cfg: SynthConfig) -> Replay:
-    """Deterministic synthetic replay (seeded)."""
+def generate(cfg: SynthConfig, workers: int = 1) -> Replay:
+    """Deterministic synthetic replay (seeded).  workers > 1 computes the
+    blocks of records on that many threads while the one seeded stream is
+    drawn in order: the replay is the same for every count."""
     rng = np.random.default_rng(cfg.seed)
     table = make_table(cfg, rng)
     if cfg.sample_seed is not None:  # same table, independent sample stream (shards)
@@ -597,27 +624,41 @@ def generate(cfg: SynthConfig) -> Replay:
     ranks = np.arange(1, K + 1, dtype=np.float64)
     pmf = ranks ** (-cfg.zipf_s)
     cdf = np.cumsum(pmf) / pmf.sum()
+    perm = _perm_cache(K, cfg.seed)
     T = cfg.nb_threads
-    per = []
     n_read = int(cfg.nb_samples * cfg.read_frac)
     n_write = cfg.nb_samples - n_read
-    captures = []  # (start time, thread, access, records)
-    for access, total in ((0, n_read), (1, n_write)):
-        for t in range(T):
-            n = total // T + (1 if t < total % T else 0)
-            if n == 0:
-                continue
-            rec = _records(n, rng, cfg, table, heap_keys, heap_first, cdf, access, T0, T0 + HORIZON)
-            for s in range(0, n, cfg.buffer_records):
+    pool = ThreadPoolExecutor(workers) if workers > 1 else None
+    blocks = []  # (thread, access, records or their future)
+    try:
+        for access, total in ((0, n_read), (1, n_write)):
+            for t in range(T):
+                n = total // T + (1 if t < total % T else 0)
+                if n == 0:
+                    continue
+                d = _draw_records(n, rng, cfg, K, access, T0, T0 + HORIZON)
+                args = (d, n, cfg, table, heap_keys, heap_first, cdf, perm, access)
+                del d
+                blocks.append((t, access, pool.submit(_finish_records, *args) if pool else _finish_records(*args)))
+                del args
+        captures = []  # (start time, thread, access, records)
+        for t, access, rec in blocks:
+            if pool:
+                rec = rec.result()
+            for s in range(0, rec.shape[0], cfg.buffer_records):
                 chunk = rec[s : s + cfg.buffer_records]
                 captures.append((int(chunk["timestamp"][0]), t, access, chunk))
+    finally:
+        if pool:
+            pool.shutdown(wait=True, cancel_futures=True)
+    del blocks
     captures.sort(key=lambda c: (c[0], c[1], c[2]))
     buffers: List[Buffer] = []
     for ts0, t, access, chunk in captures:
-        raw = np.frombuffer(chunk.tobytes(), dtype=np.uint8)
+        raw = chunk.view(np.uint8)  # (a view of its block's records: one copy less of the whole batch)
         if cfg.lost_frac > 0:
             raw = _inject_lost(raw, chunk.shape[0], cfg.lost_frac, rng)
-        buffers.append(Buffer(t, access, raw.copy(), 0, raw.shape[0]))
+        buffers.append(Buffer(t, access, raw, 0, raw.shape[0]))
     if cfg.wrap_one and buffers:
         buffers[len(buffers) // 2] = _wrap(buffers[len(buffers) // 2], rng)
     buffers.reverse()  # `samples` is LIFO: analysis order = newest capture first

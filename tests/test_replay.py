@@ -31,6 +31,43 @@ def test_generator_is_deterministic():
     assert all(np.array_equal(x.ring, y.ring) for x, y in zip(a.buffers, b.buffers))
 
 
+@pytest.mark.parametrize("kw", [
+    dict(nb_samples=30_000, nb_intervals=400, lost_frac=1e-3, wrap_one=True, seed=7),
+    dict(nb_samples=1_000, nb_intervals=3, nb_globals=0, with_stack=False),  # globals' share falls into the gaps
+    dict(nb_samples=7, nb_intervals=1, nb_threads=3),  # blocks of 2 and 1 records, empty write blocks
+    dict(nb_samples=20_000, nb_intervals=5_000, sample_seed=1003, read_frac=1.0, seed=1),
+])
+def test_generator_workers_same_replay(kw):
+    """generate(workers=N) draws the one seeded stream in order and only
+    computes the blocks on threads: the replay is that of workers=1."""
+    a = generate(SynthConfig(**kw))
+    b = generate(SynthConfig(**kw), workers=4)
+    assert a.meta == b.meta and a.nb_threads == b.nb_threads
+    assert a.table.entries.tobytes() == b.table.entries.tobytes()
+    assert len(a.buffers) == len(b.buffers) > 0
+    for x, y in zip(a.buffers, b.buffers):
+        assert (x.thread_rank, x.access_type, x.data_tail, x.data_head) == (y.thread_rank, y.access_type,
+                                                                           y.data_tail, y.data_head)
+        assert np.array_equal(x.ring, y.ring)
+
+
+PINNED_SHA256 = "1e46ef4ddb4fbf8854450315b26f2d655e493535506b12d742b9bf711b103dd1"
+
+
+def test_generator_pinned_bytes():
+    """The seeded workload is the benchmark's input: its bytes stay what they
+    were (sha256 over a small replay's table and buffers, taken from the
+    generator before it computed its blocks on threads)."""
+    import hashlib
+
+    rp = generate(SynthConfig(nb_samples=50_000, nb_intervals=500, lost_frac=1e-3, wrap_one=True, seed=7), workers=3)
+    h = hashlib.sha256()
+    h.update(rp.table.keys.tobytes() + rp.table.entries.tobytes())
+    for b in rp.buffers:
+        h.update(bytes([b.thread_rank, b.access_type]) + b.linear().tobytes())
+    assert h.hexdigest() == PINNED_SHA256
+
+
 def test_copy_buffer_semantics():
     """__copy_buffer (mem_sampling.c:675-738): [tail, head) with wrap; empty
     segments are dropped."""

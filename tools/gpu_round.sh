@@ -27,19 +27,19 @@ for s in $STAGES; do
       tail -5 $OUT/pytest_gpu_$TAG.log ;;
     bench)
       echo "== bench"
-      timeout -k 10 900 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err \
+      timeout -k 10 900 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err \
         || { echo "bench failed"; tail -40 $OUT/bench_$TAG.err; exit 1; }
       cat $OUT/bench_$TAG.json ;;
     bench3)
       echo "== bench c3"
-      timeout -k 10 900 python bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_c3_$TAG.json 2> $OUT/bench_c3_$TAG.err \
+      timeout -k 10 900 python bench.py --full --workload c3 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_c3_$TAG.json 2> $OUT/bench_c3_$TAG.err \
         || { echo "bench c3 failed"; tail -40 $OUT/bench_c3_$TAG.err; exit 1; }
       cat $OUT/bench_c3_$TAG.json ;;
     prof)
       echo "== rocprofv3 kernel trace"
       rm -rf $OUT/prof_$TAG
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof_$TAG -o run --output-format csv \
-        -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1 \
+        -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1 \
         || { echo "rocprof failed"; tail -40 $OUT/prof_$TAG.log; exit 1; }
       find $OUT/prof_$TAG -name "*kernel_stats.csv" -exec cat {} \; | head -20 ;;
     ablate)
@@ -83,7 +83,7 @@ for s in $STAGES; do
         i=$((i+1))
         rm -rf $OUT/pmc_${TAG}_$i
         timeout -k 10 400 rocprofv3 --pmc $set --kernel-trace -d $ROOT/$OUT/pmc_${TAG}_$i -o run --output-format csv \
-          -- python3 $ROOT/bench.py --workload ${PMC_WL:-c2} --steps 3 --warmup 1 --no-cpu-baseline > $OUT/pmc_${TAG}_$i.log 2>&1 \
+          -- python3 $ROOT/bench.py --full --workload ${PMC_WL:-c2} --steps 3 --warmup 1 --no-cpu-baseline > $OUT/pmc_${TAG}_$i.log 2>&1 \
           || { echo "pmc pass $i failed"; tail -20 $OUT/pmc_${TAG}_$i.log; exit 1; }
       done
       echo "pmc passes done" ;;
@@ -121,7 +121,7 @@ for s in $STAGES; do
         i=$((i+1))
         rm -rf $OUT/l2_${TAG}_$i
         timeout -k 10 400 rocprofv3 --pmc $set --kernel-trace -d $ROOT/$OUT/l2_${TAG}_$i -o run --output-format csv \
-          -- python3 $ROOT/bench.py --workload ${L2_WL:-k1m} --steps 3 --warmup 1 --no-cpu-baseline > $OUT/l2_${TAG}_$i.log 2>&1 \
+          -- python3 $ROOT/bench.py --full --workload ${L2_WL:-k1m} --steps 3 --warmup 1 --no-cpu-baseline > $OUT/l2_${TAG}_$i.log 2>&1 \
           || { echo "l2 pass $i failed"; tail -20 $OUT/l2_${TAG}_$i.log; exit 1; }
       done
       echo "l2 passes done" ;;
@@ -147,7 +147,7 @@ for s in $STAGES; do
       echo "== rocprofv3 pmc FETCH_SIZE"
       rm -rf $OUT/pmc_$TAG
       timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $ROOT/$OUT/pmc_$TAG -o run --output-format csv \
-        -- python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_$TAG.log 2>&1 \
+        -- python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_$TAG.log 2>&1 \
         || { echo "rocprof pmc failed"; tail -40 $OUT/pmc_$TAG.log; exit 1; }
       find $OUT/pmc_$TAG -name "*counter_collection.csv" -exec head -5 {} \; ;;
   esac

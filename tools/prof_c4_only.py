@@ -21,7 +21,7 @@ def main():
             break
         short = name.split("(")[0].replace("void ", "")
         stats[short].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    print(f"# rocprofv3 --kernel-trace of `bench.py --steps 10 --warmup 2 --no-cpu-baseline` ({path}):")
+    print(f"# rocprofv3 --kernel-trace of `bench.py --full --steps 10 --warmup 2 --no-cpu-baseline` ({path}):")
     print("# the c4 dispatches only (before the first attribute_kernel of the c2 secondary line)")
     for k in sorted(stats):
         v = stats[k]
