@@ -82,16 +82,12 @@ constexpr uint32_t kOldLds = 512;
 constexpr uint32_t kPnOldLds = 1u << 13, kPnOldShift = 16;
 constexpr uint32_t kPartEntries = 1536;    // entries per partition (LDS object counters)
 constexpr uint32_t kPartCells = 28672;     // u16 page cells per partition: nb_threads x cell span
-#ifndef NMG_ITEM_CHUNKS
-#define NMG_ITEM_CHUNKS 1023
-#endif
-constexpr uint32_t kItemChunks = NMG_ITEM_CHUNKS;  // chunks per work item (one workgroup): the packed object
-                                                   // counters cannot overflow; past 2^16 records a u16 page
-                                                   // cell can, and the local pass carries it (kPageCarry)
+constexpr uint32_t kItemChunks = 1023;     // chunks per work item (one workgroup): fewer than 2^16 records, so
+                                           // neither the packed object counters nor a u16 page cell can
+                                           // overflow before the item's flush
 static_assert((uint64_t)kItemChunks * kChunk < (1ull << (64 - kPackShift)), "packed count per item");
-constexpr bool kPageCarry = (uint64_t)kItemChunks * kChunk >= 65536u;
+static_assert((uint64_t)kItemChunks * kChunk < 65536u, "a u16 page cell cannot wrap within one item");
 constexpr uint32_t kChunkIdBits = 25;      // route pass LDS: chunk id << 7 | fill
-constexpr uint32_t kNoChunk = 0xffffffffu;
 constexpr uint32_t kFoundLds = 16384;      // found_kernel: per-buffer LDS counters of one workgroup
 // internal switches (tests / A/B only)
 constexpr uint32_t kDbgNoRoute = 0x10000;  // large tables: the single-pass attribute_kernel instead

@@ -7,82 +7,16 @@
 // changes nothing.  What changes is where the table lookups go: instead of a
 // directory slot and a node record in HBM per sample (two dependent random
 // lines), the route pass finds a sample's partition in a 16 KiB LDS tree and
-// writes a 24 B compact record; the local pass then resolves whole partitions
+// writes a 16 B compact record; the local pass then resolves whole partitions
 // with their keys and node records in LDS.
 #include <algorithm>
 
 #include "nmg_device.h"
 #include "nmg_route.h"
 
-// build-time A/B switches of route2_kernel (tools/ab_build.sh -D...; the
-// defaults are the shipped kernel): workgroup size, the back stage of two
-// windows at a time, the global minimum / maximum read from LDS per record
-#ifndef NMG_R2WG
-#define NMG_R2WG 768
-#endif
-#ifndef NMG_R2PAIR
-#define NMG_R2PAIR 0
-#endif
-#ifndef NMG_R2LDSMM  // (1: the shipped way; 0: per-lane register minima / maxima, measured no faster)
-#define NMG_R2LDSMM 1
-#endif
-#ifndef NMG_R2COAL  // route pass: whole-line record loads, dealt to the lanes through LDS (A/B)
-#define NMG_R2COAL 0
-#endif
-#ifndef NMG_R2ONESTORE  // route pass: one store instruction for every record stored alone (shipped: 1)
-#define NMG_R2ONESTORE 1
-#endif
-#ifndef NMG_LOCAL_ONEMATCH  // local pass: one store instruction for a chunk group's match bits (shipped: 1)
-#define NMG_LOCAL_ONEMATCH 1
-#endif
-#ifndef NMG_ABL_NOSCATTER  // (ablation only, results wrong: no record stored outside the line stage)
-#define NMG_ABL_NOSCATTER 0
-#endif
-
 namespace nmg {
 
 static_assert((uint64_t)kItemChunks * kChunk * kLaneMaxWeight < (1ull << kPackShift), "packed weight per item");
-
-// in-order rank of Eytzinger node idx >= 1 of a complete `levels`-level tree
-__device__ __forceinline__ uint32_t eytz_rank(uint32_t idx, uint32_t levels) {
-  const uint32_t d = 31 - __builtin_clz(idx);
-  return (((idx - (1u << d)) * 2 + 1) << (levels - 1 - d)) - 1;
-}
-
-// The partition of addr >= the first key: the last partition whose first key
-// <= addr.  Its
-// segment by comparisons with the (uniform) segment starts, one directory
-// slot, then a binary search over the partition starts inside that slot --
-// usually none or one: one to two dependent LDS reads instead of a search over
-// every start.
-__device__ __forceinline__ uint32_t route_partition(const RouteParams& rp, const uint64_t* s_pb,
-                                                    const uint16_t* s_pdir, uint64_t addr) {
-  uint64_t s0 = rp.seg[0].start;
-  uint32_t base = rp.seg[0].base, ns = rp.seg[0].nslots, sh = rp.seg[0].shift, ql = rp.seg[0].qlast;
-  for (uint32_t k = 1; k < rp.nseg; k++) {  // (uniform bound: only the table's segments; 7 unrolled
-    const bool in = addr >= rp.seg[k].start;   // selects cost the route pass 6 %)
-    s0 = in ? rp.seg[k].start : s0;
-    base = in ? rp.seg[k].base : base;
-    ns = in ? rp.seg[k].nslots : ns;
-    sh = in ? rp.seg[k].shift : sh;
-    ql = in ? rp.seg[k].qlast : ql;
-  }
-  const uint64_t rel = (addr - s0) >> sh;
-  const uint32_t e = s_pdir[base + (rel < ns ? (uint32_t)rel : ns - 1)];
-  uint32_t q = e & 2047u;
-  const uint32_t c = e >> 11;
-  uint32_t n = (c == kDirCntSat ? ql - q : c) + 1;  // candidates q .. q + n - 1; s_pb[q] <= addr
-  while (n > 1) {
-    const uint32_t half = n >> 1;
-    if (s_pb[q + half] <= addr) {
-      q += half;
-      n -= half;
-    } else {
-      n = half;
-    }
-  }
-  return q;
-}
 
 // ---------------------------------------------------------------------------
 // compact records (16 B, see XLayout)
@@ -212,13 +146,12 @@ struct RDesc {
 // update_counters(global_counters, ...) (mem_sampling.c:517-592) in the
 // route pass: per lane and access type, one u32 per counter pair, count << 24
 // | weight sum, for the total and for kRtGroups buckets (the common PEBS
-// levels: hits in L1, LFB, L2, L3, local RAM and remote RAM, L3 misses); the
-// NA count; and per group the minimum and maximum weight of the records whose
-// first group it is, as one u32 of two u16 fields, max << 16 | (0xffff -
-// min) (0: no record; every record makes it non-zero), kept with one packed
-// u16 max.  A record whose weight reaches 2^16, or that falls in another
+// levels: hits in L1, LFB, L2, L3, local RAM and remote RAM, L3 misses); and
+// the NA count.  A record whose weight reaches 2^16, or that falls in another
 // bucket, or in two, is counted -- those parts -- by LDS atomics.  Drained
-// every kRouteDrain windows (255 records of < 2^16 fit 24 bits).
+// every kRouteDrain windows (255 records of < 2^16 fit 24 bits).  The
+// minimum and maximum weights are not kept in registers: they go to the
+// workgroup's LDS counters per record (route_count).
 //
 // A record's level class: the hit levels x = lvl >> 3 (11 bits) when HIT,
 // else the miss levels at bit 11 when MISS (HIT beats MISS, quirk Q12).
@@ -236,36 +169,19 @@ constexpr uint32_t kRtKnown = 0x7fu | (8u << 11);
 constexpr uint32_t kRouteDrain = 128;
 constexpr uint32_t kRtOne = 1u << 24;
 struct RouteAcc {
-  uint32_t tot, na, g[kRtGroups], mm[kRtGroups];
+  uint32_t tot, na, g[kRtGroups];
 };
 __device__ __forceinline__ void racc_clear(RouteAcc& a) {
   a.tot = a.na = 0;
 #pragma unroll
-  for (int g = 0; g < kRtGroups; g++) a.g[g] = a.mm[g] = 0;
-}
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-// both u16 fields' maxima (v_pk_max_u16)
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
-  const u16x2 r = __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b));
-  return __builtin_bit_cast(uint32_t, r);
-}
-// full-wave u32 maximum (DPP, as wave_sum_u32; lanes past a row's edge read 0)
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  v = max(v, dpp0<0x111, 0xf>(v));
-  v = max(v, dpp0<0x112, 0xf>(v));
-  v = max(v, dpp0<0x114, 0xf>(v));
-  v = max(v, dpp0<0x118, 0xf>(v));
-  v = max(v, dpp0<0x142, 0xa>(v));
-  v = max(v, dpp0<0x143, 0xc>(v));
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+  for (int g = 0; g < kRtGroups; g++) a.g[g] = 0;
 }
 
 // the counting of one SAMPLE of access type ACC (a wave window lies in one
 // buffer: the caller branches on the access once); every lane of the wave
 // calls it, `valid` the ones with a SAMPLE.  The minimum / maximum of the
 // record's first group is read from LDS and updated by an LDS atomic only when
-// the record moves it (NMG_R2LDSMM=0: kept in the lane's registers until the
-// drain instead -- measured no faster).
+// the record moves it.
 template <uint32_t ACC>
 __device__ __forceinline__ void route_count(RouteAcc& a, unsigned long long (*sums)[kGlobalSums],
                                             unsigned long long (*mins)[18], unsigned long long (*maxs)[18],
@@ -283,18 +199,12 @@ __device__ __forceinline__ void route_count(RouteAcc& a, unsigned long long (*su
     gm |= in ? 1u << g : 0u;
   }
   const uint32_t fb = gm ? (kRtBucketNib >> (4 * __builtin_ctz(gm))) & 15u : 0xffu;
-#if NMG_R2LDSMM  // read the LDS minimum / maximum, an atomic when the record moves it
+  // read the LDS minimum / maximum, an atomic when the record moves it
   if (valid && gm && !big) {
     const unsigned long long mn = mins[ACC][fb], mx = maxs[ACC][fb];
     if (w < mn) atomicMin(&mins[ACC][fb], (unsigned long long)w);
     if (w > mx) atomicMax(&maxs[ACC][fb], (unsigned long long)w);
   }
-#else  // (A/B, round 6) the lane's registers, drained with the counts
-  const uint32_t pw = (valid && !big) ? ((uint32_t)w << 16) | (0xffffu - (uint32_t)w) : 0u;
-  const uint32_t first = gm & (0u - gm);  // the record's first group
-#pragma unroll
-  for (int g = 0; g < kRtGroups; g++) a.mm[g] = first == (1u << g) ? pk_max_u16(a.mm[g], pw) : a.mm[g];
-#endif
   // (rare) every other bucket, and the whole record when its weight is big
   const bool rare = valid && (big || (cls & ~kRtKnown) || (gm & (gm - 1)));
   if (__ballot(rare)) {
@@ -313,7 +223,7 @@ __device__ __forceinline__ void route_count(RouteAcc& a, unsigned long long (*su
           atomicAdd(&sums[ACC][3 + 2 * bk], 1ull);
           if (w) atomicAdd(&sums[ACC][4 + 2 * bk], (unsigned long long)w);
         }
-        if (bk != fb || big) {  // (the first group's, in registers unless big)
+        if (bk != fb || big) {  // (the first group's: done above unless big)
           atomicMin(&mins[ACC][bk], (unsigned long long)w);
           atomicMax(&maxs[ACC][bk], (unsigned long long)w);
         }
@@ -323,18 +233,7 @@ __device__ __forceinline__ void route_count(RouteAcc& a, unsigned long long (*su
 }
 
 // lanes -> the workgroup's LDS counters (every lane of the wave calls this)
-__device__ __forceinline__ void racc_drain(RouteAcc& a, unsigned long long* sums, unsigned long long* mins,
-                                           unsigned long long* maxs, int lane) {
-#pragma unroll
-  for (int g = 0; g < kRtGroups; g++) {  // the groups' minimum / maximum weights
-    if (__ballot(a.mm[g] != 0) == 0) continue;
-    const uint32_t hi = wave_max_u32(a.mm[g] >> 16), lo = wave_max_u32(a.mm[g] & 0xffffu);
-    const uint32_t bk = (kRtBucketNib >> (4 * g)) & 15u;
-    if (lane == 0) {
-      atomicMin(&mins[bk], (unsigned long long)(0xffffu - lo));
-      atomicMax(&maxs[bk], (unsigned long long)hi);
-    }
-  }
+__device__ __forceinline__ void racc_drain(RouteAcc& a, unsigned long long* sums, int lane) {
   if (__ballot(a.tot != 0) == 0) {
     racc_clear(a);
     return;
@@ -374,7 +273,7 @@ __device__ __forceinline__ void rt_stamp(RTimer& t, int i) {
 // a global load.  Ranges longer than kDescLds read the rest from global
 // memory.  In the analysis-order schedule the count slot (.pad) is the
 // index and seq = seq0 + index.
-constexpr uint32_t kDescLds = NMG_R2COAL ? 160 : 512;
+constexpr uint32_t kDescLds = 512;
 
 __device__ __forceinline__ RDesc route_desc(const RouteParams& rp, const uint4* s_desc, uint32_t r0, uint32_t i) {
   RDesc d;
@@ -434,9 +333,9 @@ __device__ __forceinline__ RDesc route_desc(const RouteParams& rp, const uint4* 
 // holds, after the workgroup's last barrier.
 
 // route2_kernel's workgroup: 12 waves (three per SIMD)
-constexpr uint32_t kR2WG = NMG_R2WG;
+constexpr uint32_t kR2WG = 768;
 // line stage: partitions q < kLineParts have an LDS line
-constexpr uint32_t kLineParts = NMG_R2COAL ? 1152 : 1280;
+constexpr uint32_t kLineParts = 1280;
 // line word (u64): line l's count (3 bits) at 3 * (l mod 8), staged slots
 // (4) at 24, given up at 28, S at 52
 typedef unsigned long long LineWord;
@@ -486,55 +385,14 @@ __device__ __forceinline__ void wload(const uint8_t* data, uint64_t off, uint32_
   r.z = make_uint2(z[0], z[1]);
 }
 
-// NMG_R2COAL: the wave window's bytes as three whole-line loads (lane l:
-// bytes 16 l, 1024 + 16 l, 2048 + 16 l of the window; the third only for
-// lanes < 32), dealt to the lanes' 40 B records through the wave's LDS stage
-struct CRec {
-  uint4 a, b, c;
-};
-__device__ __forceinline__ void cload(const uint8_t* data, uint64_t off, uint32_t len, uint32_t c, int lane,
-                                      CRec& r) {
-  off = u64of(__builtin_amdgcn_readfirstlane((uint32_t)off), __builtin_amdgcn_readfirstlane((uint32_t)(off >> 32)));
-  len = __builtin_amdgcn_readfirstlane(len);
-  c = __builtin_amdgcn_readfirstlane(c);
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(data + off), (short)0, (int)len, 0x00020000);
-  const uint32_t pos = c + uint32_t(lane) * 16u;
-  const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, pos, 0, 0);
-  const auto y = __builtin_amdgcn_raw_buffer_load_b128(rs, pos + 1024u, 0, 0);
-  const auto z = __builtin_amdgcn_raw_buffer_load_b128(rs, pos + 2048u, 0, 0);
-  r.a = make_uint4(x[0], x[1], x[2], x[3]);
-  r.b = make_uint4(y[0], y[1], y[2], y[3]);
-  r.c = make_uint4(z[0], z[1], z[2], z[3]);
-}
-__device__ __forceinline__ Rec stage_rec(uint4* st, const CRec& r, int lane) {
-  st[lane] = r.a;
-  st[64 + lane] = r.b;
-  if (lane < 32) st[128 + lane] = r.c;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(st) + 5 * lane;
-  Rec d;
-  d.hdr = q[0];
-  d.ts = q[1];
-  d.addr = q[2];
-  d.w = q[3];
-  d.dsrc = q[4];
-  return d;
-}
-#if NMG_R2COAL
-typedef CRec WRec;
-#define NMG_WLOAD(d, o, l, c, ln, r) cload(d, o, l, c, ln, r)
-#else
-typedef RawRec WRec;
-#define NMG_WLOAD(d, o, l, c, ln, r) wload(d, o, l, c, ln, r)
-#endif
-
-// route_partition with the segment table in LDS instead of kernel arguments
-// (which the compiler would keep in scalar registers): the segment is the
-// number of segment starts <= addr past the first (the starts in one group
-// of broadcast reads, the unused ones ~0), then one read of its parameters
+// The partition of addr >= the first key: the last partition whose first key
+// <= addr.  Its segment, one directory slot of that segment, then a binary
+// search over the partition starts inside that slot -- usually none or one:
+// one to two dependent LDS reads instead of a search over every start.  The
+// segment table is in LDS, not in kernel arguments (which the compiler would
+// keep in scalar registers): the segment is the number of segment starts <=
+// addr past the first (the starts in one group of broadcast reads, the unused
+// ones ~0), then one read of its parameters
 struct SegL {
   uint4 a;  // start lo, start hi, base, nslots
   uint4 b;  // shift, qlast
@@ -653,14 +511,6 @@ __device__ __forceinline__ Claim route2_settle(uint64_t old, uint32_t q, unsigne
   return r;
 }
 
-template <int N>
-__device__ __forceinline__ bool any_of(const bool (&b)[N]) {
-  bool r = false;
-#pragma unroll
-  for (int i = 0; i < N; i++) r |= b[i];
-  return r;
-}
-
 // a routed record between route2_kernel's front (stream, counters, partition,
 // encode) and its back (claim, line stage, store)
 struct XF {
@@ -676,15 +526,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
   __shared__ uint32_t s_dead[(kMaxParts + 1) / 32];
   __shared__ unsigned long long s_state[kMaxParts + 1];  // open chunk << 32 | slots claimed in it
   __shared__ uint4 s_desc[kDescLds];
-#if NMG_R2COAL
-  // per wave, used in turn: the window's bytes (front start), the slow path's
-  // SAMPLE offsets, the line write-out table (back) -- one wave's LDS ops run in order
-  __shared__ uint4 s_stage[kWaves][kWaveWinBytes / 16];
-  uint32_t(*s_wlist)[kWaveWinBytes / 4] = reinterpret_cast<uint32_t(*)[kWaveWinBytes / 4]>(s_stage);
-  uint2(*s_tab)[kWaveWinBytes / 8] = reinterpret_cast<uint2(*)[kWaveWinBytes / 8]>(s_stage);
-#else
   __shared__ uint32_t s_wlist[kWaves][64];  // slow path: the wave window's SAMPLE offsets
-#endif
   __shared__ uint32_t s_taken, s_bnext;
   __shared__ unsigned long long s_gsums[2][kGlobalSums], s_gmins[2][18], s_gmaxs[2][18];
   __shared__ SegL s_seg[kRouteSegs];
@@ -694,9 +536,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
   __shared__ uint4 s_line[kLineParts * 4];
   __shared__ LineWord s_lw[kLineParts];
   __shared__ uint32_t s_ldst[kLineParts];
-#if !NMG_R2COAL
   __shared__ uint2 s_tab[kWaves][64];
-#endif
 
   Params& p = rp.p;
   const int tid = threadIdx.x;
@@ -787,10 +627,10 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
         elen = d1.len;
       }
     };
-    WRec ra, rb;
-    NMG_WLOAD(p.data, d0.offset, d0.len, 0, lane, ra);
+    RawRec ra, rb;
+    wload(p.data, d0.offset, d0.len, 0, lane, ra);
     predict();
-    NMG_WLOAD(p.data, eoff, elen, pcur, lane, rb);
+    wload(p.data, eoff, elen, pcur, lane, rb);
 
     RTimer rt;  // (TIMING) per-wave phase cycles
 #pragma unroll
@@ -810,7 +650,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       d.ta = __builtin_amdgcn_readfirstlane(d.ta);
       d.pad = __builtin_amdgcn_readfirstlane(d.pad);
     };
-    auto front = [&](WRec& A, WRec& B, XF& X) {
+    auto front = [&](RawRec& A, RawRec& B, XF& X) {
       uni(d0);
       uni(d1);
       cur = __builtin_amdgcn_readfirstlane(cur);
@@ -823,11 +663,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
         nwin++;
       }
       rt_stamp<TIMING>(rt, 0);
-#if NMG_R2COAL
-      Rec rec = stage_rec(s_stage[wave], A, lane);
-#else
       Rec rec = decode_rec(A, pos);
-#endif
       const bool bad = cand && (uint64_t(pos) + kRecBytes > dw.len || (rec.hdr >> 48) != kRecBytes);
       bool valid;
       uint32_t roff = pos, ncur;
@@ -913,11 +749,11 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       // ---- the next window's loads again if it is not where B was loaded
       // (after a slow-path window), then the loads of the window after it
       if (d0.pad != pidx || (d0.pad != kNoBuf && cur != pcur)) {
-        NMG_WLOAD(p.data, d0.offset, d0.len, cur, lane, B);
+        wload(p.data, d0.offset, d0.len, cur, lane, B);
         vm_drain();  // (rare: keeps the waits on the common path exact)
       }
       predict();
-      NMG_WLOAD(p.data, eoff, elen, pcur, lane, A);
+      wload(p.data, eoff, elen, pcur, lane, A);
 
       // ---- this window's records: update_counters(global_counters, sample)
       // (mem_sampling.c:882: every SAMPLE, matched or not), partition, chunk
@@ -930,8 +766,8 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
         route_count<1>(gacc[1], s_gsums, s_gmins, s_gmaxs, valid, uint32_t(rec.dsrc >> 5) & 0x3fff, rec.w);
       }
       if (++gwin == kRouteDrain) {
-        racc_drain(gacc[0], s_gsums[0], s_gmins[0], s_gmaxs[0], lane);
-        racc_drain(gacc[1], s_gsums[1], s_gmins[1], s_gmaxs[1], lane);
+        racc_drain(gacc[0], s_gsums[0], lane);
+        racc_drain(gacc[1], s_gsums[1], lane);
         gwin = 0;
       }
       rt_stamp<TIMING>(rt, 2);
@@ -950,122 +786,75 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       rt_stamp<TIMING>(rt, 4);
     };
 
-    // ---- the records of N windows (one; two in the NMG_R2PAIR A/B build,
-    // their LDS round trips issued together): a slot in each record's
-    // partition's open chunks (one LDS atomic on the partition's state,
-    // route2_settle), the line stage, the stores.  (Two records of one lane
-    // behave as the records of two lanes: every step below is correct for any
-    // number of records of one partition.)  No barrier: the waves run on
-    // their own streams.
-    auto back = [&](const auto& X) {
-      constexpr int N = (int)(sizeof(X) / sizeof(X[0]));
-      uint64_t dst[N];   // rec16 slot, or ~0: no slot (not routed / overflow list)
-      uint32_t lid[N];   // the slot's chunk line number (mod 4096): the lap that serves it
-      bool ovf[N], lined[N];
-      LineWord lw[N];
-      uint32_t waitg[N];
-      bool todo[N];
-      unsigned long long old[N];
-#pragma unroll
-      for (int r = 0; r < N; r++) {
-        dst[r] = ~0ull;
-        lid[r] = 0;
-        ovf[r] = false;
-        waitg[r] = 0;
-        todo[r] = false;
-        lined[r] = X[r].routed && X[r].q < nlp;
-        // (the line word read beside the claim: a lap can only move on once
-        // this record's own line is written, so a lap that equals the
-        // record's line here still does after the claim)
-        lw[r] = lined[r] ? s_lw[X[r].q] : LineWord(0);
-      }
-#pragma unroll
-      for (int r = 0; r < N; r++) old[r] = X[r].routed ? atomicAdd(&s_state[X[r].q], 1ull) : 0ull;
-#pragma unroll
-      for (int r = 0; r < N; r++) {
-        if (X[r].routed) {
-          const Claim c = route2_settle(old[r], X[r].q, s_state, s_taken, capl, rp.cmeta, c0);
-          dst[r] = c.dst;
-          lid[r] = c.lid;
-          ovf[r] = c.ovf;
-          waitg[r] = c.waitg;
-          todo[r] = !c.ok;
-        }
-      }
+    // ---- the records of one window: a slot in each record's partition's
+    // open chunks (one LDS atomic on the partition's state, route2_settle),
+    // the line stage, the stores.  Every step below is correct for any number
+    // of records of one partition.  No barrier: the waves run on their own
+    // streams.
+    auto back = [&](const XF& X) {
+      uint64_t dst = ~0ull;  // rec16 slot, or ~0: no slot (not routed / overflow list)
+      uint32_t lid = 0;      // the slot's chunk line number (mod 4096): the lap that serves it
+      bool ovf = false, todo = false;
+      uint32_t waitg = 0;
+      const bool lined = X.routed && X.q < nlp;
+      // (the line word read beside the claim: a lap can only move on once
+      // this record's own line is written, so a lap that equals the
+      // record's line here still does after the claim)
+      const LineWord lw = lined ? s_lw[X.q] : LineWord(0);
+      const unsigned long long old = X.routed ? atomicAdd(&s_state[X.q], 1ull) : 0ull;
+      auto settle = [&](unsigned long long st) {
+        const Claim c = route2_settle(st, X.q, s_state, s_taken, capl, rp.cmeta, c0);
+        dst = c.dst;
+        lid = c.lid;
+        ovf = c.ovf;
+        waitg = c.waitg;
+        todo = !c.ok;
+      };
+      if (X.routed) settle(old);
       {
-        bool spin[N];
-#pragma unroll
-        for (int r = 0; r < N; r++) spin[r] = todo[r];
-        while (__ballot(any_of(todo))) {  // (rare) void claims
-#pragma unroll
-          for (int r = 0; r < N; r++) {
-            if (!todo[r]) continue;
-            if (!spin[r]) {
-              const Claim c = route2_settle(atomicAdd(&s_state[X[r].q], 1ull), X[r].q, s_state, s_taken, capl, rp.cmeta, c0);
-              dst[r] = c.dst;
-              lid[r] = c.lid;
-              ovf[r] = c.ovf;
-              waitg[r] = c.waitg;
-              todo[r] = !c.ok;
-              spin[r] = todo[r];
-            } else {
-              const uint64_t st = __hip_atomic_load(&s_state[X[r].q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              spin[r] = st_gen(st) == waitg[r];
-            }
+        bool spin = todo;
+        while (__ballot(todo)) {  // (rare) void claims
+          if (!todo) continue;  // (this lane's claim is settled: the others')
+          if (!spin) {
+            settle(atomicAdd(&s_state[X.q], 1ull));
+            spin = todo;
+          } else {
+            const uint64_t st = __hip_atomic_load(&s_state[X.q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            spin = st_gen(st) == waitg;
           }
         }
       }
       rt_stamp<TIMING>(rt, 5);
       // ---- the line stage (see the comment above kR2WG)
-      bool staged[N], counts[N];
-#pragma unroll
-      for (int r = 0; r < N; r++) staged[r] = counts[r] = false;
-      if (__ballot(any_of(lined))) {
-        bool done[N];
-        uint32_t dmask[N];
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          lid[r] &= kLwLineMask;
-          const uint32_t j = (uint32_t)dst[r] & 3u, S = lw_s(lw[r]), ahead = (lid[r] - S) & kLwLineMask;
-          // (a record of the overflow list has no slot but counts for its line)
-          counts[r] = lined[r] && !(lw[r] & kLwBroken) && ahead < ahead_max;
-          staged[r] = counts[r] && ahead == 0 && dst[r] != ~0ull;
-          if (lined[r] && !(lw[r] & kLwBroken) && ahead >= ahead_max) atomicOr(&s_lw[X[r].q], kLwBroken);
-          if (staged[r]) {
-            s_line[X[r].q * 4 + j] = X[r].a;
-            s_ldst[X[r].q] = (uint32_t)(dst[r] >> 2);
-          } else if (counts[r] && dst[r] != ~0ull && !NMG_R2ONESTORE) {
-            if (!NMG_ABL_NOSCATTER) rp.rec16[dst[r]] = X[r].a;
-          }
+      bool staged = false, counts = false;
+      if (__ballot(lined)) {
+        lid &= kLwLineMask;
+        const uint32_t j = (uint32_t)dst & 3u, S = lw_s(lw), ahead = (lid - S) & kLwLineMask;
+        // (a record of the overflow list has no slot but counts for its line)
+        counts = lined && !(lw & kLwBroken) && ahead < ahead_max;
+        staged = counts && ahead == 0 && dst != ~0ull;
+        if (lined && !(lw & kLwBroken) && ahead >= ahead_max) atomicOr(&s_lw[X.q], kLwBroken);
+        if (staged) {
+          s_line[X.q * 4 + j] = X.a;
+          s_ldst[X.q] = (uint32_t)(dst >> 2);
         }
         // (the staged records before the counts that may complete their lines)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        LineWord o[N];
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          o[r] = 0;
-          if (counts[r]) {
-            const uint32_t j = (uint32_t)dst[r] & 3u;
-            o[r] = atomicAdd(&s_lw[X[r].q], (kLwOne << (3 * (lid[r] & (kLwAhead - 1)))) +
-                                                (staged[r] ? kLwOne << (kLwMaskShift + j) : LineWord(0)));
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          // the line's fourth record, the line being S (S may have reached it
-          // since the read beside the claim)
-          done[r] = counts[r] && lw_count(o[r], lid[r]) == 3 && lw_s(o[r]) == lid[r];
-          dmask[r] = counts[r] ? lw_mask(o[r]) | (staged[r] ? 1u << ((uint32_t)dst[r] & 3u) : 0u) : 0u;
-          if (TIMING) rt.acc[8] += (uint64_t)__popcll(__ballot(counts[r] && !staged[r]));
-        }
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          const uint64_t dm = __ballot(done[r]);
-          if (!dm) continue;
+        LineWord o = 0;
+        if (counts)
+          o = atomicAdd(&s_lw[X.q], (kLwOne << (3 * (lid & (kLwAhead - 1)))) +
+                                        (staged ? kLwOne << (kLwMaskShift + j) : LineWord(0)));
+        // the line's fourth record, the line being S (S may have reached it
+        // since the read beside the claim)
+        const bool done = counts && lw_count(o, lid) == 3 && lw_s(o) == lid;
+        const uint32_t dmask = counts ? lw_mask(o) | (staged ? 1u << j : 0u) : 0u;
+        if (TIMING) rt.acc[8] += (uint64_t)__popcll(__ballot(counts && !staged));
+        const uint64_t dm = __ballot(done);
+        if (dm) {
           // the staged slots of the completed lines written out: four lanes per line
-          if (done[r])
+          if (done)
             s_tab[wave][__popcll(dm & ((1ull << lane) - 1))] =
-                make_uint2(X[r].q | (dmask[r] << 11) | (lid[r] << 16), (uint32_t)(dst[r] >> 2));
+                make_uint2(X.q | (dmask << 11) | (lid << 16), (uint32_t)(dst >> 2));
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
           __builtin_amdgcn_wave_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
@@ -1096,38 +885,33 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
               piece_done(t, k);
             }
           }
-          // (s_tab reused by the second record's lines: every lane read its entry above)
+          // (s_tab is reused by the next window's lines: every lane read its entry above)
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
           __builtin_amdgcn_wave_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
         }
       }
       rt_stamp<TIMING>(rt, 9);
-#pragma unroll
-      for (int r = 0; r < N; r++) {
-        // the records the line stage did not take: not lined, or given up
-        const bool straight = dst[r] != ~0ull && !counts[r];
-        // (NMG_R2ONESTORE: the records counted for a line ahead of the staged one
-        // stored here too -- one store instruction for every record stored
-        // alone; nothing reads the slots before the local pass)
-        const bool alone = straight || (NMG_R2ONESTORE && counts[r] && !staged[r] && dst[r] != ~0ull);
-        if (alone && !NMG_ABL_NOSCATTER) rp.rec16[dst[r]] = X[r].a;
-        if (TIMING) {  // (records staged / stored straight to their slot)
-          rt.acc[6] += (uint64_t)__popcll(__ballot(staged[r]));
-          rt.acc[7] += (uint64_t)__popcll(__ballot(straight));
-        }
+      // the records the line stage did not take: not lined, or given up
+      const bool straight = dst != ~0ull && !counts;
+      // (the records counted for a line ahead of the staged one stored here
+      // too -- one store instruction for every record stored alone; nothing
+      // reads the slots before the local pass)
+      const bool alone = straight || (counts && !staged && dst != ~0ull);
+      if (alone) rp.rec16[dst] = X.a;
+      if (TIMING) {  // (records staged / stored straight to their slot)
+        rt.acc[6] += (uint64_t)__popcll(__ballot(staged));
+        rt.acc[7] += (uint64_t)__popcll(__ballot(straight));
       }
-      if (__ballot(any_of(ovf))) {  // (rare) a workgroup's pool outgrown: SAMPLEs shorter than 40 B
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          if (!ovf[r]) continue;
-          const uint64_t pbq = s_pb[X[r].q];
+      if (__ballot(ovf)) {  // (rare) a workgroup's pool outgrown: SAMPLEs shorter than 40 B
+        if (ovf) {
+          const uint64_t pbq = s_pb[X.q];
           const uint32_t o = atomicAdd(rp.ovf_cnt, 1u);
           if (o < rp.ovf_cap) {
-            rp.ovf16[o] = X[r].a;
+            rp.ovf16[o] = X.a;
             rp.ovfx[o] = pbq;
           } else {  // attributed at once
-            XRec xr = x_decode(rp.xl, pbq, X[r].a);
+            XRec xr = x_decode(rp.xl, pbq, X.a);
             if (xr.esc) x_resolve(xr, rp.xl, p.data, p.sbufs);
             direct_attribute(p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, 0, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
                              xr.g(rp.xl));
@@ -1138,22 +922,13 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       rt_stamp<TIMING>(rt, 10);
     };
 
-#if NMG_R2PAIR
-    XF X[2];  // (A/B: the back of two windows at a time -- measured slower, round 6)
+    XF X;
     do {  // (d0: the wave's stream, uniform)
-      front(ra, rb, X[0]);
-      front(rb, ra, X[1]);
+      front(ra, rb, X);
+      back(X);
+      front(rb, ra, X);
       back(X);
     } while (d0.pad != kNoBuf);
-#else
-    XF X[1];
-    do {  // (d0: the wave's stream, uniform)
-      front(ra, rb, X[0]);
-      back(X);
-      front(rb, ra, X[0]);
-      back(X);
-    } while (d0.pad != kNoBuf);
-#endif
 
     if (TIMING && lane == 0) {
       unsigned long long* o = p.dbg + (uint64_t(blockIdx.x) * (kWG / 64) + tid / 64) * kRouteTimingWords;
@@ -1167,8 +942,8 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       o[12] = rt.acc[10];
     }
   }
-  racc_drain(gacc[0], s_gsums[0], s_gmins[0], s_gmaxs[0], lane);
-  racc_drain(gacc[1], s_gsums[1], s_gmins[1], s_gmaxs[1], lane);
+  racc_drain(gacc[0], s_gsums[0], lane);
+  racc_drain(gacc[1], s_gsums[1], lane);
   lds_sync();
 #pragma unroll
   for (uint32_t a = 0; a < 2; a++) {  // the global mem_counters of both access types
@@ -1369,11 +1144,6 @@ __global__ __launch_bounds__(kWG) void scatter_kernel(ScatterParams r) {
 // local pass: workgroup size and chunks per interleaved group (a wave holds
 // two groups: one being attributed, the other's records in flight)
 constexpr uint32_t kLWG = 1024;
-// u16 page cells of items past 2^16 records (kPageCarry): at kCarryAt a
-// cell moves kCarryMove of its count to global memory (at most kLWG * 2
-// adds are in flight, far fewer than 2^16 - kCarryAt)
-constexpr uint32_t kCarryAt = 0xf000u, kCarryMove = 0x8000u;
-static_assert(2 * kLWG < 0x10000u - kCarryAt && kCarryMove < kCarryAt, "page cell carry margin");
 constexpr int kLC = 2;  // (the timing wait below counts on it)
 
 // a load served by L2, never by this CU's L1 (global_load ... sc1)
@@ -1420,7 +1190,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   __shared__ unsigned long long s_first[kPartEntries];
   __shared__ uint32_t s_pg[kPartCells / 2];
   __shared__ uint32_t s_clist[kItemChunks];  // the item's chunk list entries
-  __shared__ uint32_t s_item, s_cnext, s_nfound, s_big, s_took, s_carry;
+  __shared__ uint32_t s_item, s_cnext, s_nfound, s_big, s_took;
   __shared__ uint4 s_nx[4];  // the next item's work item and PartInfo (take_next)
 
   Params& p = lp.p;
@@ -1520,7 +1290,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     const uint32_t ncell = (pages && pi.pages_lds) ? T * pi.span : 0u;
     const bool excl = item.w != 0 && !(p.flags & kDbgLocalAtomics);  // no other workgroup writes this partition's
                                                                      // counters
-    if (tid == 0) s_big = s_carry = 0;
+    if (tid == 0) s_big = 0;
     lds_sync();
     const uint64_t k0key = u64of(__builtin_amdgcn_readfirstlane((uint32_t)s_keys[0]),
                                  __builtin_amdgcn_readfirstlane((uint32_t)(s_keys[0] >> 32)));
@@ -1754,8 +1524,8 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         vm_drain();
       }
       // the chunks' match bits (per-buffer counts, found_kernel) straight to
-      // global memory, and this wave's matched total
-#if NMG_LOCAL_ONEMATCH  // (lane j stores chunk j's bits: one store instruction for the group)
+      // global memory (lane j stores chunk j's bits: one store instruction for
+      // the group), and this wave's matched total
       {
         uint64_t mine = 0;
         uint32_t ml = 0;
@@ -1768,14 +1538,6 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         }
         if (lane < kLC && ml < nl) lp.cmatch[s_clist[ml] & ((1u << kChunkIdBits) - 1)] = mine;
       }
-#else
-#pragma unroll
-      for (int j = 0; j < kLC; j++) {
-        const uint64_t fm = __ballot(erel[j] >= 0);
-        nfound += (uint32_t)__popcll(fm);
-        if (lane == 0 && li[j] < nl) lp.cmatch[s_clist[li[j]] & ((1u << kChunkIdBits) - 1)] = fm;
-      }
-#endif
       rt_stamp<TIMING>(rt, 3);
       const bool noobj = (p.flags & kDbgLocalNoObj) != 0;
 #pragma unroll
@@ -1813,44 +1575,15 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       if (pages && !(p.flags & kDbgLocalNoPage)) {
         // ma_get_block: page_no = (int)((addr - buffer_addr) / 4096) (mem_analyzer.c:530-531)
         uint32_t page[kLC];
-        bool glob = false, carry[kLC];
+        bool glob = false;
 #pragma unroll
         for (int j = 0; j < kLC; j++) {
           page[j] = uint32_t(int(pofs[j] / kPageSize));
-          carry[j] = false;
-          if (erel[j] >= 0 && hrel[j] != kEmpty32 && ncell) {
+          if (erel[j] >= 0 && hrel[j] != kEmpty32 && ncell) {  // (a u16 cell: an item has < 2^16 records)
             const uint32_t c = xr[j].th * pi.span + hrel[j] + page[j], sh = 16 * (c & 1);
-            if (kPageCarry) {  // (an item past 2^16 records: a cell could wrap its u16)
-              const uint32_t o = atomicAdd(&s_pg[c >> 1], 1u << sh);
-              carry[j] = ((o >> sh) & 0xffffu) == kCarryAt - 1;
-            } else {
-              atomicAdd(&s_pg[c >> 1], 1u << sh);
-            }
+            atomicAdd(&s_pg[c >> 1], 1u << sh);
           }
           glob |= erel[j] >= 0 && (hrel[j] == kEmpty32 || !ncell);
-        }
-        if (kPageCarry) {
-          bool anyc = false;
-#pragma unroll
-          for (int j = 0; j < kLC; j++) anyc |= carry[j];
-          // (rare) a cell reached kCarryAt: kCarryMove of its count go to the
-          // histogram in global memory.  Exactly one add brings a cell from
-          // kCarryAt - 1 to kCarryAt (only adds raise it, and the move takes it
-          // far below), and fewer adds than 2^16 - kCarryAt can be in flight
-          // in the workgroup before the move lands: no u16 wraps, no borrow
-          // crosses into the neighbouring cell.
-          if (__ballot(anyc)) {
-            if (lane == 0) s_carry = 1;  // (the flush then adds to the cells instead of storing them)
-#pragma unroll
-            for (int j = 0; j < kLC; j++) {
-              if (!carry[j]) continue;
-              const uint32_t rel = hrel[j] + page[j], c = xr[j].th * pi.span + rel;
-              atomicSub(&s_pg[c >> 1], kCarryMove << (16 * (c & 1)));
-              const uint64_t cell = (PACKED && pi.cmap != ~0u) ? (uint64_t)lp.pe_cmap[pi.cmap + rel] : pi.cb + rel;
-              atomicAdd(p.hist + uint64_t(xr[j].th) * p.hist_cells + cell, kCarryMove);
-            }
-            vm_drain();
-          }
         }
         if (__ballot(glob)) {  // (rare) cells in global memory: dense or sparse
 #pragma unroll
@@ -1902,7 +1635,6 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     // first ordinals from ~0, page cells from zero
     const bool clean = excl && lp.fresh && __builtin_amdgcn_readfirstlane(lp.ctl[3]) == 0;
     const bool clean_obj = clean && __builtin_amdgcn_readfirstlane(s_big) == 0;
-    const bool clean_pg = clean && __builtin_amdgcn_readfirstlane(s_carry) == 0;
     // the item's counters to global memory, consecutive lanes on consecutive
     // words, each LDS word zeroed for the next item as it is read; the only
     // item of its partition adds with plain loads and stores (no other
@@ -1962,7 +1694,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
             uint64_t cell = pi.cb + rel;
             if (cmap != ~0u) cell = cnt[u][h] ? lp.pe_cmap[cmap + rel] : 0u;  // (online: packed cells)
             pc[u][h] = p.hist + uint64_t(th) * p.hist_cells + cell;
-            old[u][h] = (excl && !clean_pg && cnt[u][h]) ? l2_load(pc[u][h]) : 0u;
+            old[u][h] = (excl && !clean && cnt[u][h]) ? l2_load(pc[u][h]) : 0u;
           }
         }
 #pragma unroll

@@ -213,11 +213,11 @@ def test_route_settled_partitions_keep_timestamp_zero(tmp_path):
 
 def test_route_hot_page_cell_past_u16(tmp_path):
     """One cell taking most of an item's records: a Zipf(3) hot object of one
-    page, one thread, so a work item of the local pass puts far more than
-    2^16 samples on one u16 LDS page cell when items hold more than 2^16
-    records (kPageCarry: the cell moves kCarryMove to global memory at
-    kCarryAt); the counts must still equal the oracle's, and the hot cell
-    must be past 2^16."""
+    page, one thread, so one page cell receives more than 3 * 2^16 samples
+    over many work items of the local pass.  Each item holds fewer than 2^16
+    records and flushes its u16 LDS page cells before they can wrap, so the
+    cell stays exact: the counts must equal the oracle's, and the hot cell
+    must be past 3 * 2^16."""
     d = str(tmp_path)
     cfg = SynthConfig(nb_samples=600_000, nb_intervals=3_000, nb_threads=1, size_min=64, size_max=4000, zipf_s=3.0,
                       frac_gap=0.0, frac_stack=0.0, frac_global=0.0, reuse_frac=0.0, realloc_frac=0.0, seed=82)

@@ -1,6 +1,10 @@
 #!/bin/bash
-# Build a variant of libnumamma_gpu.so with extra -D flags into build_ab/:
-#   tools/ab_build.sh NAME "-DFOO=1 -DBAR=2"
+# Build this tree's libnumamma_gpu.so a second time, as build_ab/lib_NAME.so,
+# for an A/B against another build (tools/ab_lib.sh):
+#   tools/ab_build.sh NAME ["extra compiler flags"]
+# The kernels carry no build-time variants: the other side of an A/B is
+# another checkout (or an edited copy) of numamma_amd/ built the same way.
+# Needs build/nmg_report.o and build/nmg_replay.o of a finished `make`.
 set -e
 cd "$(dirname "$0")/../numamma_amd"
 NAME=$1; DEFS=$2

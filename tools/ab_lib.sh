@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of two builds of libnumamma_gpu.so on one box (NMG_LIB_PATH):
 #   gpurun -- bash tools/ab_lib.sh build_ab/lib_a.so build_ab/lib_b.so[:FLAGS] [more.so ...]
-# (:FLAGS: NMG_BENCH_DEBUG_FLAGS for that run, e.g. lib.so:0x20000000 for route_kernel)
+# (:FLAGS: NMG_BENCH_DEBUG_FLAGS for that run, e.g. lib.so:0x20000000 for the route pass without its LDS line stage)
 # Alternates the libraries twice over bench.py's line (AB_WL, default c4) and
 # prints the analysis time split (route / rest) of each run.
 set -o pipefail

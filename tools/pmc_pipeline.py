@@ -6,8 +6,8 @@ bench.py's roofline.traffic.
     python tools/pmc_pipeline.py --workload c4 --fetch DIR --write DIR [--out FILE]
 
 FETCH_SIZE and WRITE_SIZE are KiB per dispatch.  gfx950 tallies a wide
-coalesced streaming read at half its bytes; the record streams (route_kernel:
-the 40 B records; local_kernel: the 24 B compact records; attribute_kernel:
+coalesced streaming read at half its bytes; the record streams (route2_kernel:
+the 40 B records; local_kernel: the 16 B compact records; attribute_kernel:
 the 40 B records) are such reads, so their kernels' FETCH_SIZE is doubled
 (an upper bound for their small table loads); the other kernels' reads are
 taken as counted.  The output carries the kernel-source hash
@@ -23,9 +23,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PIPELINE = ("route2_kernel", "route_kernel", "overflow_kernel", "count_kernel", "plan_kernel", "scatter_kernel", "local_kernel",
+PIPELINE = ("route2_kernel", "overflow_kernel", "count_kernel", "plan_kernel", "scatter_kernel", "local_kernel",
             "attribute_kernel", "reduce")
-STREAMING = ("route2_kernel", "route_kernel", "local_kernel", "attribute_kernel")
+STREAMING = ("route2_kernel", "local_kernel", "attribute_kernel")
 
 
 def per_kernel(d):
@@ -52,7 +52,7 @@ def main():
     from numamma_amd.srchash import kernel_source_hash
 
     fetch, write = per_kernel(args.fetch), per_kernel(args.write)
-    first = next(k for k in ("route2_kernel", "route_kernel", "attribute_kernel") if k in fetch)
+    first = next(k for k in ("route2_kernel", "attribute_kernel") if k in fetch)
     launches = fetch[first][1]
     wlaunches = write[first][1]
     kernels = {}
