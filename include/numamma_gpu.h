@@ -53,10 +53,13 @@ extern "C" {
 /* engine flags */
 #define NMG_F_MATCH_SAMPLES 0x1  /* settings.match_samples (numamma.h.in:27) */
 #define NMG_F_PAGE_HIST 0x2      /* per-(object, page, thread) counts for callsite_counters_<id>.dat */
-#define NMG_F_OBJECT_LEVELS 0x4  /* per-object level buckets (count, sum) for callsite_summary_<id>.dat */
-#define NMG_F_SAMPLE_MATCHES 0x8 /* keep every SAMPLE record's match (object or none) for the dump modes */
+#define NMG_F_OBJECT_LEVELS 0x4  /* per-object level buckets (count, sum) for callsite_summary_<id>.dat and
+                                    nmg_get_object_levels; any table size, the partition-first passes included */
+#define NMG_F_SAMPLE_MATCHES 0x8 /* keep every SAMPLE record's match (object or none) for the dump modes; any table
+                                    size; batch analyses only (nmg_stream_begin rejects it) */
 #define NMG_F_SINGLE_PASS 0x10   /* large tables (> 1023 keys): one attribution pass with global lookups instead of
-                                    the partition-first passes; same results (A/B and tests) */
+                                    the partition-first passes; same results, every other flag included
+                                    (A/B and tests) */
 #define NMG_F_DEFAULT (NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST)
 /* every public flag: nmg_create rejects any other bit with NMG_ERR_INVALID */
 #define NMG_F_ALL (NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST | NMG_F_OBJECT_LEVELS | NMG_F_SAMPLE_MATCHES | NMG_F_SINGLE_PASS)

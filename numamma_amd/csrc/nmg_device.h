@@ -73,6 +73,27 @@ __device__ __forceinline__ uint32_t bucket_mask(uint32_t lvl) {
   return 0;
 }
 
+// NMG_F_OBJECT_LEVELS: one matched SAMPLE of level field `lvl` and weight w in
+// entry e's level row of its access type (update_counters on the object's
+// counters, mem_sampling.c:517-592: na_miss, then per set level group the hit
+// or the miss bucket's count and weight sum; HIT beats MISS, quirk Q12).
+// Global u64 atomics: every kernel that attributes adds here.  n > 1: that
+// many samples of this entry, access type and level field at once, w their
+// weight sum (local_kernel merges a wave's equal ones).
+__device__ __forceinline__ void level_count(const Params& p, uint64_t e, uint32_t access, uint32_t lvl, uint64_t w,
+                                            unsigned long long n = 1ull) {
+  unsigned long long* lv = reinterpret_cast<unsigned long long*>(
+      p.sum64 + 2 * kGlobalSums + uint64_t(p.nb_entries) * 4 + (e * 2 + access) * kLevelWords);
+  if (lvl & LVL_NA) atomicAdd(lv, n);
+  for (int g = 0; g < 9; g++) {
+    if (!(lvl & level_mask(g))) continue;
+    int bucket = (lvl & LVL_HIT) ? g : ((lvl & LVL_MISS) ? 9 + g : -1);
+    if (bucket < 0) continue;
+    atomicAdd(lv + 1 + 2 * bucket, n);
+    if (w) atomicAdd(lv + 2 + 2 * bucket, (unsigned long long)w);
+  }
+}
+
 __device__ __forceinline__ void set_error(const Params& p, uint64_t seq, uint32_t off, uint32_t code) {
   uint64_t w = (seq << 40) | (uint64_t(off) << 8) | code;
   atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + 36 + p.nb_entries),

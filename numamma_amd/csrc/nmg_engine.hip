@@ -455,10 +455,11 @@ extern "C" int nmg_analyze(nmg_engine* h) {
   rc = upload_buffers(h);
   if (rc) return rc;
   const uint32_t nb = (uint32_t)h->descs.size();
+  size_t smatch_words = 0;
   if (h->flags & NMG_F_SAMPLE_MATCHES) {  // one u32 per 8 B of the buffers' arena span
     uint64_t span = 0;
     for (const BufDesc& d : h->descs) span = std::max<uint64_t>(span, d.offset + d.len);
-    const size_t need = (size_t)(span / 8 + 1);
+    const size_t need = smatch_words = (size_t)(span / 8 + 1);
     if (need > h->smatch_cap) {
       HIP_TRY(h, hipStreamSynchronize(h->stream));
       (void)hipFree(h->d_smatch);
@@ -474,6 +475,10 @@ extern "C" int nmg_analyze(nmg_engine* h) {
       rc = build_schedule(h, grid, false);
       if (rc) return rc;
     }
+    // dump modes: the partition-first passes write the match of the records
+    // they route; a SAMPLE that is never routed (below the first key, in a
+    // settled partition) must read "no match" too
+    if (smatch_words) HIP_TRY(h, hipMemsetAsync(h->d_smatch, 0, smatch_words * 4, h->stream));
     return route_analyze(h, nb, grid);
   }
   if (nb && (resched || grid != h->sched_grid || h->sched_route)) {
@@ -703,10 +708,12 @@ extern "C" int nmg_debug_phase_times(nmg_engine* h, float* first_ms, float* rest
 }
 
 // Internal (not in include/numamma_gpu.h): analyses (streamed chunks) that
-// took the partition-first path so far (tests)
+// took the partition-first path so far (tests); a multi-GPU handle: its
+// workers' (call it after nmg_synchronize)
 extern "C" int nmg_debug_route_count(nmg_engine* h, uint64_t* n) {
   if (!h || !n) return NMG_ERR_INVALID;
   *n = h->route_launches;
+  for (nmg_engine* w : h->workers) *n += w->route_launches;
   return NMG_OK;
 }
 

@@ -360,18 +360,7 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
     }
   }
   sub_stamp<TIMING>(st, 3);
-  if (p.flags & NMG_F_OBJECT_LEVELS) {
-    unsigned long long* lv = reinterpret_cast<unsigned long long*>(
-        p.sum64 + 2 * kGlobalSums + uint64_t(p.nb_entries) * 4 + (uint64_t(e) * 2 + access) * kLevelWords);
-    if (lvl & LVL_NA) atomicAdd(lv, 1ull);
-    for (int g = 0; g < 9; g++) {
-      if (!(lvl & level_mask(g))) continue;
-      int bucket = (lvl & LVL_HIT) ? g : ((lvl & LVL_MISS) ? 9 + g : -1);
-      if (bucket < 0) continue;
-      atomicAdd(lv + 1 + 2 * bucket, 1ull);
-      if (w) atomicAdd(lv + 2 + 2 * bucket, (unsigned long long)w);
-    }
-  }
+  if (p.flags & NMG_F_OBJECT_LEVELS) level_count(p, uint64_t(e), access, lvl, w);
 }
 
 // ---------------------------------------------------------------------------

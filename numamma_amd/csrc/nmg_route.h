@@ -23,7 +23,10 @@
 //                     workgroup at a time: the partition's keys and node records
 //                     in LDS, its object and page counters in LDS, flushed once
 //                     per item (__match_sample, :594-673; ma_get_block,
-//                     mem_analyzer.c:494-534);
+//                     mem_analyzer.c:494-534); with NMG_F_OBJECT_LEVELS /
+//                     NMG_F_SAMPLE_MATCHES also the matched records' level
+//                     buckets (data_src re-read from the raw record) and every
+//                     record's match (Params::smatch);
 //   5. found_kernel   per-buffer matched-sample counts from the match bits
 //                     local_kernel leaves per chunk (on demand: the reference
 //                     only sums them, mem_sampling.c:334-335, 357-361).

@@ -76,6 +76,16 @@ __device__ __forceinline__ void x_resolve(XRec& r, const XLayout& xl, const uint
   r.w = q[3];
 }
 
+// data_src.mem_lvl of the raw record at arena position pos (data_src follows
+// the weight).  The compact record has no room for it: the kernels that count
+// per-object levels re-read it for the records that matched.  A SAMPLE
+// shorter than 40 B is read the same way, as attribute_kernel and the route
+// pass's update_counters read it (load_rec: 40 B from the record's start,
+// which the stream walk checked to lie inside the buffer).
+__device__ __forceinline__ uint32_t raw_mem_lvl(const uint8_t* data, uint64_t pos) {
+  return uint32_t(reinterpret_cast<const uint64_t*>(data + pos)[4] >> 5) & 0x3fff;
+}
+
 // ---------------------------------------------------------------------------
 // direct attribution (overflow_kernel: a route workgroup's chunk pool was
 // exhausted): the lookup of
@@ -83,7 +93,9 @@ __device__ __forceinline__ void x_resolve(XRec& r, const XLayout& xl, const uint
 // memory -- binary search of the keys (ht_lower_key, tools/hash.c:63-77),
 // node record, older entries -- and global atomics.  Correct for any input;
 // only taken when a workgroup's samples outgrow its pool (SAMPLE records
-// shorter than 40 B, or the kDbgTinyPool test switch).
+// shorter than 40 B, or the kDbgTinyPool test switch).  lvl = the record's
+// data_src.mem_lvl (read with NMG_F_OBJECT_LEVELS only); slot = its buffer's
+// index in p.sbufs (analysis order).
 __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr, uint64_t ts, uint64_t w, uint32_t th,
                                                  uint32_t acc, uint32_t lvl, uint64_t seq, uint32_t off,
                                                  uint32_t slot) {
@@ -113,8 +125,12 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
     const uint4 d = q[3];
     if (d.x > 1) match_older(p, d.y, d.x, addr, ts, m);
   }
+  // (dump modes: the host zeroed the words before the route pass, so a record
+  // that returned above keeps "no match")
+  if (p.smatch) p.smatch[(p.sbufs[slot].offset + off) >> 3] = m.e >= 0 ? (uint32_t)m.e + 1u : 0u;
   if (m.e < 0) return;
   const uint64_t e = (uint64_t)m.e;
+  if (p.flags & NMG_F_OBJECT_LEVELS) level_count(p, e, acc, lvl, w);
   atomicAdd(p.bufcnt + p.nb_bufs + slot, 1u);
   atomicAdd(p.found, 1ull);
   atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, acc, 0, p.nb_entries)), 1ull);
@@ -516,6 +532,7 @@ __device__ __forceinline__ Claim route2_settle(uint64_t old, uint32_t q, unsigne
 struct XF {
   uint4 a;     // the compact record
   uint32_t q;  // its partition
+  uint32_t lvl;  // data_src.mem_lvl (the direct attribution past a full overflow list)
   bool routed;
 };
 
@@ -781,6 +798,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       rt_stamp<TIMING>(rt, 3);
       X.a = make_uint4(0, 0, 0, 0);
       X.q = q;
+      X.lvl = uint32_t(rec.dsrc >> 5) & 0x3fff;
       X.routed = routed;
       if (routed) X.a = x_encode(rp.xl, s_pb[q], rec.addr, rec.ts, rec.w, dw.pad, roff, dw.thread_rank(), acc_l);
       rt_stamp<TIMING>(rt, 4);
@@ -913,7 +931,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
           } else {  // attributed at once
             XRec xr = x_decode(rp.xl, pbq, X.a);
             if (xr.esc) x_resolve(xr, rp.xl, p.data, p.sbufs);
-            direct_attribute(p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, 0, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
+            direct_attribute(p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, X.lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
                              xr.g(rp.xl));
           }
         }
@@ -984,7 +1002,10 @@ __global__ __launch_bounds__(256) void overflow_kernel(RouteParams rp) {
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     XRec xr = x_decode(rp.xl, rp.ovfx[i], rp.ovf16[i]);
     if (xr.esc) x_resolve(xr, rp.xl, rp.p.data, rp.p.sbufs);
-    direct_attribute(rp.p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, 0, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
+    const uint32_t lvl = (rp.p.flags & NMG_F_OBJECT_LEVELS)
+                             ? raw_mem_lvl(rp.p.data, rp.p.sbufs[xr.g(rp.xl)].offset + xr.off(rp.xl))
+                             : 0u;
+    direct_attribute(rp.p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
                      xr.g(rp.xl));
   }
 }
@@ -1177,8 +1198,11 @@ __device__ __forceinline__ int32_t match_older_pos(const Params& p, uint32_t fir
 }
 
 // PACKED: an online table with packed page cells (LocalParams::pe_cmap; a
-// variant of its own, so that the offline table's flush carries none of it)
-template <bool TIMING, bool PACKED>
+// variant of its own, so that the offline table's flush carries none of it).
+// EXTRA: the outputs of NMG_F_OBJECT_LEVELS and NMG_F_SAMPLE_MATCHES (the
+// extras block at the end of `process`; again a variant of its own: the
+// instances without it are the code they were before it existed)
+template <bool TIMING, bool PACKED, bool EXTRA>
 __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   __shared__ uint64_t s_keys[kPartSlots];
   __shared__ uint4 s_pn[kPartSlots];  // packed node records (PackedNode)
@@ -1203,6 +1227,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   for (int k = 0; k < 12; k++) rt.acc[k] = 0;
   rt.last = TIMING ? stamp() : 0;
   uint32_t nchunks = 0, nit = 0;
+  uint64_t textra = 0;  // (TIMING) cycles of the extras block
   uint32_t nfound = 0;  // this wave's matched records (Params::found, added once per workgroup at the end)
   if (tid == 0) s_nfound = 0;  // (read after the item loop's barriers)
   // the item counters start zeroed; every flush re-zeroes what it reads
@@ -1601,6 +1626,81 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         }
       }
       rt_stamp<TIMING>(rt, 5);
+      if (EXTRA) {
+        // The extras: every record's match at its arena position
+        // (Params::smatch, as attribute_kernel leaves it), and the matched
+        // records' level buckets.  The compact record carries no data_src, so
+        // a matched record's is re-read from the raw record at the record's
+        // location (as x_resolve re-reads an escaped record).  A block of its
+        // own behind a ballot that ends in vm_drain, like the other paths
+        // with global memory ops of their own: only the chunk's live lanes
+        // (below its fill; for the levels, matched) form an address or issue
+        // a load.  The level rows take global u64 atomics, as in
+        // attribute_kernel; the id is the entry id, so an online table's map
+        // applies.
+        const bool lev = (p.flags & NMG_F_OBJECT_LEVELS) != 0;
+        bool need[kLC], any = false;
+#pragma unroll
+        for (int j = 0; j < kLC; j++) {
+          need[j] = valid[j] && (p.smatch != nullptr || (lev && erel[j] >= 0));
+          any |= need[j];
+        }
+        if (__ballot(any)) {
+          // the needed lanes' loads and match stores (no cross-lane step here)
+          uint64_t eid[kLC];
+          uint32_t lvl[kLC];
+          bool row[kLC];  // a level row to add to
+#pragma unroll
+          for (int j = 0; j < kLC; j++) {
+            eid[j] = 0;
+            lvl[j] = 0;
+            row[j] = false;
+            if (!need[j]) continue;
+            const uint64_t pos = lp.descs[xr[j].g(lp.xl)].offset + xr[j].off(lp.xl);
+            const bool hit = erel[j] >= 0;
+            if (hit) eid[j] = entry_id(lp, pi.e0 + (uint32_t)erel[j]);
+            if (p.smatch) p.smatch[pos >> 3] = hit ? (uint32_t)eid[j] + 1u : 0u;
+            if (lev && hit) {
+              lvl[j] = raw_mem_lvl(p.data, pos);
+              row[j] = true;
+            }
+          }
+          // The level rows.  A chunk holds one partition's records, and a hot
+          // object's come in runs: the chunk's records of one (entry, access,
+          // level field) are added at once by one lane -- their number and
+          // their weight sum -- group after group in lane order (one round
+          // per distinct triple of the chunk: at most 64).  Per-record atomics
+          // from every lane put the same words of a hot object under atomics
+          // from every wave: 213 ms per step at the configs[3] shard against
+          // 31 ms.  Weights from kLaneMaxWeight on stay out of
+          // the u32 wave sum and add their own.
+          if (lev) {
+#pragma unroll
+            for (int j = 0; j < kLC; j++) {
+              const uint32_t key = ((uint32_t)erel[j] << 15) | (xr[j].acc << 14) | lvl[j];
+              const bool small = row[j] && w[j] < kLaneMaxWeight;
+              uint64_t todo = __ballot(small);
+              while (todo) {
+                const uint32_t lead = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(todo));
+                const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)lead);
+                const bool same = small && key == k;  // (all still to do: a key's lanes leave together)
+                const uint64_t sm = __ballot(same);
+                const uint32_t ws = wave_sum_u32(same ? (uint32_t)w[j] : 0u);
+                if ((uint32_t)lane == lead)
+                  level_count(p, eid[j], xr[j].acc, lvl[j], ws, (unsigned long long)__popcll(sm));
+                todo &= ~sm;
+              }
+              if (row[j] && !small) level_count(p, eid[j], xr[j].acc, lvl[j], w[j]);
+            }
+          }
+          vm_drain();
+        }
+        if (TIMING) {
+          const uint64_t now = stamp();
+          textra += now - rt.last;
+          rt.last = now;
+        }
+      }
     };
     uint4 A[kLC], B[kLC];
     auto grab = [&]() -> uint32_t {
@@ -1632,8 +1732,11 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     // an item alone on its partition whose counters nothing else wrote since
     // the reset (no overflow-path record in this launch, no large weight in
     // this item) stores them without reading: counts and weights from zero,
-    // first ordinals from ~0, page cells from zero
-    const bool clean = excl && lp.fresh && __builtin_amdgcn_readfirstlane(lp.ctl[3]) == 0;
+    // first ordinals from ~0, page cells from zero.  (The large-weight path
+    // and this store-without-read concern the count and weight rows only:
+    // the level rows of NMG_F_OBJECT_LEVELS always take atomics -- the extras
+    // block, direct_attribute -- so neither `fresh` nor s_big knows of them.)
+    const bool clean =excl && lp.fresh && __builtin_amdgcn_readfirstlane(lp.ctl[3]) == 0;
     const bool clean_obj = clean && __builtin_amdgcn_readfirstlane(s_big) == 0;
     // the item's counters to global memory, consecutive lanes on consecutive
     // words, each LDS word zeroed for the next item as it is read; the only
@@ -1721,6 +1824,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     o[11] = rt.acc[9];
     o[12] = rt.acc[10];
     o[13] = rt.acc[11];
+    o[14] = textra;
   }
 }
 
@@ -1793,14 +1897,22 @@ hipError_t launch_scatter(uint32_t grid, hipStream_t s, const ScatterParams& r) 
   return hipGetLastError();
 }
 
+template <bool TIMING, bool PACKED>
+static void launch_local_as(bool extra, uint32_t grid, hipStream_t s, const LocalParams& r) {
+  if (extra) hipLaunchKernelGGL((local_kernel<TIMING, PACKED, true>), dim3(grid), dim3(kLWG), 0, s, r);
+  else hipLaunchKernelGGL((local_kernel<TIMING, PACKED, false>), dim3(grid), dim3(kLWG), 0, s, r);
+}
+
+// the extras variant for engines with per-object levels or per-sample matches
 hipError_t launch_local(uint32_t grid, hipStream_t s, const LocalParams& r) {
   const bool timing = (r.p.flags & kDbgLocalTiming) != 0, packed = r.pe_cmap != nullptr;
+  const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr;
   if (packed) {
-    if (timing) hipLaunchKernelGGL((local_kernel<true, true>), dim3(grid), dim3(kLWG), 0, s, r);
-    else hipLaunchKernelGGL((local_kernel<false, true>), dim3(grid), dim3(kLWG), 0, s, r);
+    if (timing) launch_local_as<true, true>(extra, grid, s, r);
+    else launch_local_as<false, true>(extra, grid, s, r);
   } else {
-    if (timing) hipLaunchKernelGGL((local_kernel<true, false>), dim3(grid), dim3(kLWG), 0, s, r);
-    else hipLaunchKernelGGL((local_kernel<false, false>), dim3(grid), dim3(kLWG), 0, s, r);
+    if (timing) launch_local_as<true, false>(extra, grid, s, r);
+    else launch_local_as<false, false>(extra, grid, s, r);
   }
   return hipGetLastError();
 }

@@ -193,13 +193,12 @@ void route_segments(const uint64_t* b, uint32_t P, RSeg* seg, uint32_t* nseg, st
 // have their page cells in id order, scattered over the address order, so
 // its partitions are not cut by cells (the cells of a partition whose span is
 // too wide for LDS take global atomics).  Only for engines that count per
-// object (NMG_F_MATCH_SAMPLES) without the dump modes' per-sample output or
-// per-object levels; otherwise the table keeps attribute_kernel.
+// object (NMG_F_MATCH_SAMPLES); the dump modes' per-sample output and the
+// per-object levels are outputs of the local pass too (local_kernel's extras).
 int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t K,
                             const std::vector<DevEntry>& dev, const uint32_t* ids) {
   free_route_table(h);
-  if (K <= kLdsNodes || !(h->flags & NMG_F_MATCH_SAMPLES) || (h->flags & (NMG_F_SAMPLE_MATCHES | NMG_F_OBJECT_LEVELS)))
-    return NMG_OK;
+  if (K <= kLdsNodes || !(h->flags & NMG_F_MATCH_SAMPLES)) return NMG_OK;
   if (ids) {  // the identity map is the offline case
     uint32_t e = 0;
     while (e < entry_off[K] && ids[e] == e) e++;

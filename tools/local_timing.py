@@ -10,6 +10,8 @@ shader cycles per wave:
   match    per chunk: node record, dates, older entries, match-bit word
   object   per chunk: packed object counters + first-match ordinal
   page     per chunk: page cells
+  extras   per chunk: per-object levels (data_src re-read from the raw record,
+           level atomics) and per-sample matches, with --flags 0x7 / 0xf
   dequeue  per item: next work item (+ barrier)
   setup    per item: partition table into LDS, counters cleared (+ barrier)
   flush    per item: waiting for the item's slowest wave, counters to global memory
@@ -76,12 +78,14 @@ def main():
         for k, name in enumerate(PHASES):
             per = ch if k < 6 else it
             out[f"{name}_cyc_per_{'chunk' if k < 6 else 'item'}"] = float(a[:, k].sum() / per)
-        out["imbalance_cyc_per_item"] = float(a[:, 11].sum() / it)  # waiting for the item's slowest wave
+        # (--flags with 0x4 / 0x8: the level atomics and per-sample matches, after the page cells)
+        out["extras_cyc_per_chunk"] = float(a[:, 14].sum() / ch)
+        out["imbalance_cyc_per_item"] =float(a[:, 11].sum() / it)  # waiting for the item's slowest wave
         recs = ch * 64
         out["exact_node_frac"] = float(a[:, 12].sum() / recs)  # decided on the exact node record (global)
         out["key_search_frac"] = float(a[:, 13].sum() / recs)  # lookups that read keys past the directory
-        out["total_cyc_per_wave"] = float((a[:, :9].sum(axis=1) + a[:, 11]).mean())
-        out["max_total_cyc_per_wave"] = float((a[:, :9].sum(axis=1) + a[:, 11]).max())
+        out["total_cyc_per_wave"] = float((a[:, :9].sum(axis=1) + a[:, 11] + a[:, 14]).mean())
+        out["max_total_cyc_per_wave"] = float((a[:, :9].sum(axis=1) + a[:, 11] + a[:, 14]).max())
         print(json.dumps(out), flush=True)
         e.close()
         del d
