@@ -46,155 +46,10 @@ extern "C" int nmg_get_last_error_detail(nmg_engine* h, char* buf, size_t len) {
   return NMG_OK;
 }
 
-void free_counters(nmg_engine* h) {
-  (void)hipFree(h->d_sum64);
-  (void)hipFree(h->d_min64);
-  (void)hipFree(h->d_max64);
-  (void)hipFree(h->d_hist);
-  (void)hipFree(h->d_sparse_keys);
-  (void)hipFree(h->d_sparse_vals);
-  h->d_sum64 = h->d_min64 = h->d_max64 = nullptr;
-  h->d_hist = nullptr;
-  h->d_sparse_keys = nullptr;
-  h->d_sparse_vals = nullptr;
-  (void)hipFree(h->d_sparse_ck);
-  h->d_sparse_ck = nullptr;
-  (void)hipFree(h->d_objcw);
-  h->d_objcw = nullptr;
-  h->objcw_cap = 0;
-  (void)hipFree(h->d_sparse_dirty);
-  h->d_sparse_dirty = nullptr;
-  (void)hipFree(h->d_pk64);
-  h->d_pk64 = nullptr;
-  (void)hipFree(h->d_tlog);
-  h->d_tlog = nullptr;
-  h->tlog_bytes = 0;
-  (void)hipFree(h->d_tlog_cnt);
-  h->d_tlog_cnt = nullptr;
-  h->tlog_cnt_cap = 0;
-}
-
-// the lookup structures of one table (keys, node records, LDS tree or fences
-// + directory, table-order entries)
-void free_lookup(nmg_engine* h) {
-  (void)hipFree(h->d_keys);
-  (void)hipFree(h->d_nodes);
-  (void)hipFree(h->d_efences);
-  (void)hipFree(h->d_enodes);
-  (void)hipFree(h->d_ffences);
-  (void)hipFree(h->d_fshift);
-  (void)hipFree(h->d_dir);
-  if (h->d_chain != h->d_entries) (void)hipFree(h->d_chain);
-  h->d_keys = nullptr;
-  h->d_nodes = nullptr;
-  h->d_efences = nullptr;
-  h->d_enodes = nullptr;
-  h->d_ffences = nullptr;
-  h->d_fshift = nullptr;
-  h->d_dir = nullptr;
-  h->d_chain = nullptr;
-}
-
-// the partitions of the partition-first path (built with the table)
-void free_route_table(nmg_engine* h) {
-  (void)hipFree(h->d_parts);
-  (void)hipFree(h->d_pbounds);
-  (void)hipFree(h->d_pdir);
-  (void)hipFree(h->d_pdead);
-  (void)hipFree(h->d_pe_keys);
-  (void)hipFree(h->d_pe_nodes);
-  (void)hipFree(h->d_pe_info);
-  (void)hipFree(h->d_pe_pnode);
-  (void)hipFree(h->d_pe_old);
-  (void)hipFree(h->d_pe_oinf);
-  (void)hipFree(h->d_pe_dir);
-  (void)hipFree(h->d_pe_ids);
-  (void)hipFree(h->d_pe_lrel);
-  (void)hipFree(h->d_pe_cmap);
-  h->d_pe_dir = nullptr;
-  h->d_pe_ids = nullptr;
-  h->d_pe_lrel = nullptr;
-  h->d_pe_cmap = nullptr;
-  h->d_parts = nullptr;
-  h->d_pbounds = nullptr;
-  h->d_pdir = nullptr;
-  h->d_pdead = nullptr;
-  h->d_pe_keys = nullptr;
-  h->d_pe_nodes = nullptr;
-  h->d_pe_info = nullptr;
-  h->d_pe_pnode = nullptr;
-  h->d_pe_old = nullptr;
-  h->d_pe_oinf = nullptr;
-  h->route_ok = false;
-  h->nparts = 0;
-}
-
-// the per-analysis buffers of the partition-first path
-void free_route_pool(nmg_engine* h) {
-  for (void* q : {(void*)h->d_rec16, (void*)h->d_cmeta, (void*)h->d_cmatch, (void*)h->d_clist,
-                  (void*)h->d_items, (void*)h->d_chunk0, (void*)h->d_used, (void*)h->d_pcnt, (void*)h->d_pbase,
-                  (void*)h->d_ctl, (void*)h->d_ovf16, (void*)h->d_ovfx})
-    (void)hipFree(q);
-  h->d_rec16 = nullptr;
-  h->d_cmeta = nullptr;
-  h->d_cmatch = nullptr;
-  h->d_clist = nullptr;
-  h->d_items = nullptr;
-  h->d_chunk0 = nullptr;
-  h->d_used = nullptr;
-  h->d_pcnt = nullptr;
-  h->d_pbase = nullptr;
-  h->d_ctl = nullptr;
-  h->d_ovf16 = nullptr;
-  h->d_ovfx = nullptr;
-  h->ovf_cap = 0;
-  h->route_chunk_cap = h->items_cap = h->route_grid_cap = 0;
-  h->route_pending = false;
-}
-
-
-LookupSet take_lookup(nmg_engine* h) {
-  LookupSet l{h->d_keys, h->d_nodes, h->d_efences, h->d_enodes, h->d_ffences, h->d_fshift, h->d_dir, h->d_chain,
-              h->K, h->elevels, h->nb_fences, h->fence_log2, h->dir_log2};
-  h->d_keys = nullptr;
-  h->d_nodes = nullptr;
-  h->d_efences = nullptr;
-  h->d_enodes = nullptr;
-  h->d_ffences = nullptr;
-  h->d_fshift = nullptr;
-  h->d_dir = nullptr;
-  h->d_chain = nullptr;
-  return l;
-}
-
-void put_lookup(nmg_engine* h, const LookupSet& l) {
-  h->d_keys = l.keys;
-  h->d_nodes = l.nodes;
-  h->d_efences = l.efences;
-  h->d_enodes = l.enodes;
-  h->d_ffences = l.ffences;
-  h->d_fshift = l.fshift;
-  h->d_dir = l.dir;
-  h->d_chain = l.chain;
-  h->K = l.K;
-  h->elevels = l.elevels;
-  h->nb_fences = l.nb_fences;
-  h->fence_log2 = l.fence_log2;
-  h->dir_log2 = l.dir_log2;
-}
-
 void free_table(nmg_engine* h) {
-  free_route_table(h);
-  free_lookup(h);
-  (void)hipFree(h->d_entries);
-  h->d_entries = nullptr;
-}
-
-hipError_t alloc_copy(nmg_engine* h, void** dptr, const void* src, size_t bytes) {
-  hipError_t e = hipMalloc(dptr, bytes ? bytes : 16);
-  if (e != hipSuccess) return e;
-  if (bytes) return hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, h->stream);
-  return hipSuccess;
+  h->rt = RouteTable();
+  h->lk = LookupSet();
+  h->d_entries.reset();
 }
 
 // keys strictly ascending, every key with >= 1 entry, entry_off a prefix array over n entries
@@ -326,35 +181,18 @@ extern "C" void nmg_destroy(nmg_engine* h) {
   if (!h) return;
   multi_destroy(h);
   (void)hipSetDevice(h->device);
+  // every stream and upload drained, then the handles destroyed; `delete`
+  // releases the device and pinned buffers (their owners' destructors)
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  free_table(h);
-  free_counters(h);
-  free_route_pool(h);
-  for (const auto& r : h->hostregs) (void)hipHostUnregister(r.pages);
-  (void)hipFree(h->d_cells_rows);
-  (void)hipFree(h->d_arena);
-  (void)hipFree(h->d_descs);
-  (void)hipFree(h->d_bufcnt);
-  (void)hipFree(h->d_found);
-  (void)hipFree(h->d_scratch);
-  (void)hipFree(h->d_sdescs);
-  (void)hipFree(h->d_ranges);
-  (void)hipFree(h->d_dbg);
-  (void)hipFree(h->d_smatch);
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
   if (h->up_recorded) (void)hipEventSynchronize(h->up_ev);
-  if (h->up_ev) (void)hipEventDestroy(h->up_ev);
-  (void)hipHostFree(h->up_pin);
-  for (void* q : {(void*)h->cprep.d_base, (void*)h->cprep.d_off, (void*)h->cprep.d_part, (void*)h->cprep.d_np,
-                  (void*)h->cprep.d_cnt, (void*)h->cprep.d_sent, (void*)h->cprep.d_soff})
-    (void)hipFree(q);
-  snap_free(h);
+  if (h->snap.stream) (void)hipStreamSynchronize(h->snap.stream);
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+  for (const auto& r : h->hostregs) (void)hipHostUnregister(r.pages);
+  if (h->up_ev) (void)hipEventDestroy(h->up_ev);
+  if (h->snap.ready) (void)hipEventDestroy(h->snap.ready);
+  if (h->snap.copied) (void)hipEventDestroy(h->snap.copied);
+  if (h->snap.stream) (void)hipStreamDestroy(h->snap.stream);
   for (auto& sl : h->slots) {
-    if (sl.h_stage) (void)hipHostFree(sl.h_stage);
-    if (sl.h_sdescs) (void)hipHostFree(sl.h_sdescs);
-    (void)hipFree(sl.d_arena);
-    (void)hipFree(sl.d_sdescs);
     if (sl.copied) (void)hipEventDestroy(sl.copied);
     if (sl.done) (void)hipEventDestroy(sl.done);
   }
@@ -404,25 +242,25 @@ extern "C" int nmg_reset_counters(nmg_engine* h) {
   h->route_pending = false;  // the counts found_kernel would add are zeroed here
   ResetParams r;
   memset(&r, 0, sizeof(r));
-  r.sum64 = h->d_sum64;
+  r.sum64 = h->cnt.d_sum64;
   r.n_sum64 = h->n_sum64;
-  r.min64 = h->d_min64;
+  r.min64 = h->cnt.d_min64;
   r.n_min64 = h->n_min64;
-  r.max64 = h->d_max64;
+  r.max64 = h->cnt.d_max64;
   r.n_max64 = h->n_max64;
   r.found = h->d_found;
   const uint64_t hist_bytes = h->hist_cells * h->T * 4;
-  if (hist_bytes & 15) HIP_TRY(h, hipMemsetAsync(h->d_hist, 0, hist_bytes, h->stream));  // (16 B multiple always)
-  r.hist = reinterpret_cast<uint4*>(h->d_hist);
+  if (hist_bytes & 15) HIP_TRY(h, hipMemsetAsync(h->cnt.d_hist, 0, hist_bytes, h->stream));  // (16 B multiple always)
+  r.hist = reinterpret_cast<uint4*>(h->cnt.d_hist.get());
   r.n_hist16 = hist_bytes / 16;
-  if (h->d_sparse_keys) {
-    r.sparse_keys = h->d_sparse_keys;
-    r.sparse_vals = h->d_sparse_vals;
+  if (h->cnt.d_sparse_keys) {
+    r.sparse_keys = h->cnt.d_sparse_keys;
+    r.sparse_vals = h->cnt.d_sparse_vals;
     r.sparse_cap = h->sparse_cap;
     // reset #n reads the flag the analyses since reset #n-1 set, and clears
     // the one the analyses after it will set
-    r.sparse_read = h->d_sparse_dirty + (h->nreset & 1);
-    r.sparse_clear = h->d_sparse_dirty + ((h->nreset + 1) & 1);
+    r.sparse_read = h->cnt.d_sparse_dirty + (h->nreset & 1);
+    r.sparse_clear = h->cnt.d_sparse_dirty + ((h->nreset + 1) & 1);
   }
   // (a pending descriptor upload zeroes the per-buffer counts itself)
   if (h->d_bufcnt && (h->streaming || h->streamed || (!h->descs_dirty && !h->descs.empty()))) {
@@ -460,18 +298,15 @@ extern "C" int nmg_analyze(nmg_engine* h) {
     uint64_t span = 0;
     for (const BufDesc& d : h->descs) span = std::max<uint64_t>(span, d.offset + d.len);
     const size_t need = smatch_words = (size_t)(span / 8 + 1);
-    if (need > h->smatch_cap) {
+    if (need > h->d_smatch.cap()) {
       HIP_TRY(h, hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_smatch);
-      h->d_smatch = nullptr;
-      HIP_TRY(h, hipMalloc(&h->d_smatch, need * 4));
-      h->smatch_cap = need;
+      HIP_TRY(h, h->d_smatch.reserve(need));
     }
   }
   const uint32_t grid = attribution_grid(h, nb);
   if (route_eligible(h)) {
     if (nb && (resched || grid != h->sched_grid || !h->sched_route ||
-               h->route_sched_key != (h->nparts | ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u)))) {
+               h->route_sched_key != (h->rt.nparts | ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u)))) {
       rc = build_schedule(h, grid, false);
       if (rc) return rc;
     }
@@ -523,7 +358,7 @@ extern "C" int nmg_synchronize(nmg_engine* h) {
   }
   if (!h->have_table) return NMG_OK;
   uint64_t w = ~0ull;
-  HIP_TRY(h, hipMemcpy(&w, h->d_min64 + 36 + h->E, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(&w, h->cnt.d_min64 + 36 + h->E, 8, hipMemcpyDeviceToHost));
   return decode_error_word(h, w);
 }
 

@@ -9,6 +9,9 @@
 //   nmg_route_host.hip  the partition-first path's host side (pools, launches)
 //   nmg_results.hip     result getters, page cells, merge arrays, sparse cells
 //   nmg_multi.hip       multi-GPU handles (RCCL group reduce / device merge)
+// Device and pinned host memory is held in DevBuf / PinBuf members
+// (nmg_buffer.h): the engine and its sub-structs own their blocks, a group is
+// released by assigning an empty one, and `delete` releases the rest.
 #pragma once
 
 #include <dlfcn.h>
@@ -31,6 +34,7 @@
 #include <thread>
 #include <vector>
 
+#include "nmg_buffer.h"
 #include "nmg_kernels.h"
 #include "nmg_route.h"
 
@@ -99,6 +103,87 @@ struct CopyPool {
   }
 };
 
+struct nmg_engine;
+
+// The lookup structures of one table and their shape (keys, node records, LDS
+// tree or fences + directory, table-order entries).  Built beside the current
+// one and moved in on success (nmg_update_objects).
+struct LookupSet {
+  DevBuf<uint64_t> keys;
+  DevBuf<DevEntry> nodes;
+  DevBuf<uint64_t> efences;  // small tables: Eytzinger-ordered keys / node records
+  DevBuf<DevEntry> enodes;
+  DevBuf<uint64_t> ffences;  // large tables: Eytzinger fences, directory shifts, directory
+  DevBuf<uint8_t> fshift;
+  DevBuf<uint2> dir;
+  DevBuf<DevEntry> own_chain;  // table-order entries of an nmg_update_objects table; empty while
+                               // the table order is the id order (nmg_set_objects)
+  DevEntry* chain = nullptr;   // what the kernels read: own_chain, or the engine's d_entries
+  uint32_t K = 0, elevels = 0, nb_fences = 0, fence_log2 = 0, dir_log2 = 0;
+};
+
+// the partitions of the partition-first path (nmg_route.h), built with the table
+struct RouteTable {
+  bool ok = false;  // partitions built for the current table
+  uint32_t nparts = 0;
+  DevBuf<PartInfo> d_parts;
+  DevBuf<uint64_t> d_pbounds;  // [kMaxParts + 1] partition starts, ascending
+  DevBuf<uint16_t> d_pdir;     // [kRouteDir] the route pass's directory over them
+  DevBuf<uint32_t> d_pdead;    // [(kMaxParts + 1) / 32] partitions no sample with ts != 0 can match
+  DevBuf<uint64_t> d_pe_keys;  // [nparts][kPartSlots]
+  DevBuf<uint4> d_pe_nodes;    // [nparts][kPartSlots][2]
+  DevBuf<uint4> d_pe_pnode;    // [nparts][kPartSlots] packed node records (PackedNode)
+  DevBuf<uint4> d_pe_old;      // [nparts][kOldLds] older entries, packed
+  DevBuf<uint32_t> d_pe_oinf;  // [nparts][kOldLds]
+  DevBuf<uint2> d_pe_info;     // [nparts][kPartSlots]
+  DevBuf<uint4> d_pe_dir;      // [nparts][kPartDir] (PartDir)
+  DevBuf<uint32_t> d_pe_ids;   // [table entries] entry id per table position (online tables; else empty)
+  DevBuf<uint32_t> d_pe_lrel;  // [table entries] first packed LDS cell (online tables)
+  DevBuf<uint32_t> d_pe_cmap;  // packed cell -> histogram cell (online tables)
+};
+
+// the per-analysis buffers of the partition-first path, sized together
+// (route_pool): chunks = d_cmeta.cap(), grid = d_used.cap()
+struct RoutePool {
+  DevBuf<uint4> d_rec16;  // chunk pool: [chunks][kChunk] (addr, ts) and X words
+  DevBuf<uint32_t> d_cmeta;
+  DevBuf<unsigned long long> d_cmatch;
+  DevBuf<uint32_t> d_clist;
+  DevBuf<uint4> d_items;
+  DevBuf<uint32_t> d_chunk0;  // [grid + 1]
+  DevBuf<uint32_t> d_used;    // [grid]
+  DevBuf<uint32_t> d_pcnt;    // [grid][nparts]
+  DevBuf<uint32_t> d_pbase;   // [nparts]
+  DevBuf<uint32_t> d_ctl;     // [3] items, dequeue head, overflow records
+  DevBuf<uint4> d_ovf16;      // overflow list (route pass, pool exhausted)
+  DevBuf<unsigned long long> d_ovfx;
+};
+
+// the counter arrays of one table (nmg_set_objects releases them with it)
+struct Counters {
+  DevBuf<uint64_t> d_sum64, d_min64, d_max64;
+  DevBuf<uint32_t> d_hist;
+  DevBuf<uint64_t> d_sparse_keys;
+  DevBuf<uint32_t> d_sparse_vals;
+  DevBuf<uint64_t> d_objcw;         // [entries][4] per-object counters laid out for the D2H
+  DevBuf<uint64_t> d_sparse_ck;     // [sparse_cap + 1] compacted (key, count) words + the count (sparse_download)
+  DevBuf<uint32_t> d_sparse_dirty;  // [2] parity flags (see reset_kernel)
+  DevBuf<unsigned long long> d_pk64;  // hashed object mode: packed long-tail counters (0 between launches)
+  DevBuf<uint4> d_tlog;             // hashed object mode: long-tail log (see Params::tlog)
+  DevBuf<uint32_t> d_tlog_cnt;
+};
+
+// The table's page-cell layout on the device and the per-entry work arrays of
+// one page-cell pass over it: the synchronous getters (CellsPrep) and the
+// results snapshot (ResSnap) each keep one.
+struct CellLayout {
+  uint64_t E = 0, nsent = 0;
+  bool meta_dirty = true;  // hist_base / npages / sparse entries changed: re-upload
+  DevBuf<uint64_t> d_base, d_off, d_part, d_soff;
+  DevBuf<uint32_t> d_np, d_cnt, d_sent;
+  int ensure(nmg_engine* h, uint64_t E, uint64_t nsent);  // (re)allocated when the table outgrows them
+};
+
 struct nmg_engine {
   int device = 0;
   uint32_t flags = NMG_F_DEFAULT;
@@ -117,8 +202,8 @@ struct nmg_engine {
   // object table
   bool have_table = false;
   // results epoch: bumped by every call that can change a counter; the page
-  // cells counted by nmg_count_page_cells stay on the device (cells_*) until
-  // nmg_get_page_cells of the same epoch copies them out
+  // cells counted by nmg_count_page_cells stay on the device (cprep.d_rows)
+  // until nmg_get_page_cells of the same epoch copies them out
   uint64_t epoch = 1, cells_epoch = 0;
   // the counter arrays hold what the last reset wrote (no analysis, import or
   // table update since): the local pass may store instead of adding
@@ -133,57 +218,37 @@ struct nmg_engine {
   };
   std::vector<HostReg> hostregs;
   std::vector<uint64_t> zc_dev;
-  int64_t cells_n = 0;
-  void* d_cells_rows = nullptr;  // uint4 [cells_n] dense rows (sparse rows: cells_sparse)
-  size_t cells_rows_cap = 0;
-  struct SparseRows {
-    uint64_t off;  // first row
-    uint32_t e;
-    std::vector<std::pair<uint64_t, uint32_t>> cells;  // ((thread << 32 | page), count)
-  };
-  std::vector<SparseRows> cells_sparse;
   // results snapshot (nmg_results_begin / nmg_results_end, nmg_results.hip)
   struct ResSnap {
     hipStream_t stream = nullptr;
     hipEvent_t ready = nullptr, copied = nullptr;
     bool pending = false;
-    bool meta_dirty = true;            // hist_base / npages / sparse entries changed: re-upload
-    uint64_t E = 0, nb = 0, nsent = 0, rows_dev = 0, rows_host = 0, sparse_cap = 0;
-    uint64_t *d_base = nullptr, *d_off = nullptr, *d_part = nullptr, *d_soff = nullptr;
-    uint32_t *d_np = nullptr, *d_cnt = nullptr, *d_sent = nullptr;
-    uint64_t *d_sum = nullptr, *d_min = nullptr, *d_max = nullptr, *d_objcw = nullptr, *d_found = nullptr;
-    uint32_t* d_bufcnt = nullptr;
-    uint64_t* d_ck = nullptr;          // the sparse table's used slots, compacted (+ their count)
-    void* d_rows = nullptr;            // uint4 rows
+    CellLayout lay;
+    DevBuf<uint64_t> d_sum, d_min, d_max, d_objcw, d_found;
+    DevBuf<uint32_t> d_bufcnt;
+    DevBuf<uint64_t> d_ck;  // the sparse table's used slots, compacted (+ their count)
+    DevBuf<uint4> d_rows;
     // pinned host copies
-    uint64_t *h_sum = nullptr, *h_min = nullptr, *h_max = nullptr, *h_objcw = nullptr, *h_small = nullptr,
-             *h_soff = nullptr;        // h_small: [0] matched total, [1] rows, [2] sparse cells
-    uint32_t* h_bufcnt = nullptr;
-    uint32_t* h_rows = nullptr;        // mapped: copy_rows_kernel writes it
-    uint64_t h_cap_E = 0, h_cap_nb = 0, h_cap_sent = 0;
+    PinBuf<uint64_t> h_sum, h_min, h_max, h_objcw, h_small, h_soff;  // h_small: [0] matched total, [1] rows,
+                                                                     // [2] sparse cells
+    PinBuf<uint32_t> h_bufcnt;
+    PinBuf<uint32_t> h_rows;           // [rows][4], mapped: copy_rows_kernel writes it
     std::vector<uint32_t> sent_entry;  // begin-time table: sparse idx -> entry (~0: no longer sparse)
   } snap;
   uint64_t snap_nb = 0;  // buffers of the snapshot in flight
-  // the synchronous page-cell getters' device buffers (cells_prepare), kept across calls
+  // the synchronous page-cell getters' state (cells_prepare), kept across calls
   struct CellsPrep {
-    uint64_t E = 0, nsent = 0;
-    bool meta_dirty = true;
-    uint64_t *d_base = nullptr, *d_off = nullptr, *d_part = nullptr, *d_soff = nullptr;
-    uint32_t *d_np = nullptr, *d_cnt = nullptr, *d_sent = nullptr;
+    CellLayout lay;
+    DevBuf<uint4> d_rows;  // [n] dense rows, on the device until copied out
+    int64_t n = 0;         // rows, dense and sparse
+    // the sparse table's cells as downloaded ((key, count) words), the sparse
+    // entries of that table and their first rows: placed by cells_fill
+    std::vector<uint64_t> sparse_kv, soff;
+    std::vector<uint32_t> sent_entry;
   } cprep;
-  uint32_t K = 0, E = 0;
-  uint64_t* d_keys = nullptr;
-  DevEntry* d_nodes = nullptr;
-  uint64_t* d_efences = nullptr;  // small tables: Eytzinger-ordered keys / node records
-  DevEntry* d_enodes = nullptr;
-  uint32_t elevels = 0;
-  DevEntry* d_entries = nullptr;  // by entry id (the nmg_set_objects table)
-  DevEntry* d_chain = nullptr;    // table order of the current lookup table; == d_entries until
-                                  // the first nmg_update_objects
-  uint64_t* d_ffences = nullptr;  // large tables: Eytzinger fences, directory shifts, directory
-  uint8_t* d_fshift = nullptr;
-  uint2* d_dir = nullptr;
-  uint32_t nb_fences = 0, fence_log2 = 0, dir_log2 = 0;
+  uint32_t E = 0;
+  LookupSet lk;
+  DevBuf<DevEntry> d_entries;  // by entry id (the nmg_set_objects table)
   std::vector<uint64_t> hist_base, npages, buffer_size, entry_addr;
   std::vector<DevEntry> dev_entries;  // host copy of d_entries (nmg_update_objects builds from it)
   std::vector<nmg_object> objects;  // each entry as the latest table lists it (the report's objects)
@@ -195,64 +260,44 @@ struct nmg_engine {
   uint64_t sparse_cap = 1u << 20;
 
   // counters
-  uint64_t *d_sum64 = nullptr, *d_min64 = nullptr, *d_max64 = nullptr;
+  Counters cnt;
   uint64_t n_sum64 = 0, n_min64 = 0, n_max64 = 0;
-  uint32_t* d_hist = nullptr;
-  unsigned long long* d_found = nullptr;  // matched SAMPLEs since the last reset (Params::found)
-  uint64_t* d_scratch = nullptr;          // [2] small device results (nmg_hist_pack / unpack)
-  uint64_t* d_sparse_keys = nullptr;
-  uint32_t* d_sparse_vals = nullptr;
-  uint64_t* d_objcw = nullptr;       // [objcw_cap][4] per-object counters laid out for the D2H
-  uint64_t objcw_cap = 0;
-  uint64_t* d_sparse_ck = nullptr;  // [sparse_cap + 1] compacted (key, count) words + the count (sparse_download)
-  uint32_t* d_sparse_dirty = nullptr;  // [2] parity flags (see reset_kernel)
-  uint32_t* d_smatch = nullptr;        // NMG_F_SAMPLE_MATCHES: per 8 B of the arena span
-  unsigned long long* d_pk64 = nullptr;  // hashed object mode: packed long-tail counters (0 between launches)
-  uint4* d_tlog = nullptr;  // hashed object mode: long-tail log (see Params::tlog)
-  size_t tlog_bytes = 0;
-  uint32_t* d_tlog_cnt = nullptr;
-  size_t tlog_cnt_cap = 0;
-  size_t smatch_cap = 0;
+  DevBuf<unsigned long long> d_found;  // matched SAMPLEs since the last reset (Params::found)
+  DevBuf<uint64_t> d_scratch;          // [2] small device results (nmg_hist_pack / unpack) + range counts
+  DevBuf<uint32_t> d_smatch;           // NMG_F_SAMPLE_MATCHES: per 8 B of the arena span
   uint64_t nreset = 0;
 
   // buffers
   std::vector<BufDesc> descs;
   std::vector<uint64_t> buf_bytes;
-  uint8_t* h_stage = nullptr;
-  size_t stage_cap = 0, stage_len = 0;
-  uint8_t* d_arena = nullptr;
-  size_t arena_cap = 0;
+  PinBuf<uint8_t> h_stage;
+  size_t stage_len = 0;
+  DevBuf<uint8_t> d_arena;
   const uint8_t* d_data = nullptr;
   bool external = false;
   bool staged_dirty = false;
-  BufDesc* d_descs = nullptr;
-  size_t descs_cap = 0;
-  BufDesc* d_sdescs = nullptr;   // descriptors in stream-sorted schedule order
-  uint32_t* d_ranges = nullptr;  // per-workgroup [begin, end) in d_order
-  size_t sdescs_cap = 0, ranges_cap = 0;
+  DevBuf<BufDesc> d_descs;
+  DevBuf<BufDesc> d_sdescs;   // descriptors in stream-sorted schedule order
+  DevBuf<uint32_t> d_ranges;  // per-workgroup [begin, end) in d_order
   // pinned staging of an analysis' small uploads (descriptors, schedule,
   // chunk pools): copied on the engine stream without a host wait
-  uint8_t* up_pin = nullptr;
-  size_t up_cap = 0, up_off = 0;
+  PinBuf<uint8_t> up_pin;
+  size_t up_off = 0;
   hipEvent_t up_ev = nullptr;
   bool up_recorded = false;
   uint32_t sched_grid = 0;       // grid the current schedule was built for
   bool descs_dirty = false;
   bool multi_staged = false;  // the workers' arenas hold the current buffers (multi_analyze)
-  uint32_t* d_bufcnt = nullptr;
-  size_t bufcnt_cap = 0;     // buffers the per-buffer count array holds ([2][bufcnt_stride] u32)
+  DevBuf<uint32_t> d_bufcnt;  // per-buffer counts, [2][bufcnt_stride] u32 of [2][d_bufcnt.cap() / 2]
   size_t bufcnt_stride = 0;
 
   // streaming (nmg_stream_begin): two staging halves, each a chunk in flight
   struct StreamSlot {
-    uint8_t* h_stage = nullptr;  // pinned
-    size_t cap = 0, len = 0;
-    uint8_t* d_arena = nullptr;
-    size_t dcap = 0;
-    BufDesc* h_sdescs = nullptr;  // pinned schedule (sorted descriptors, then ranges)
-    size_t hs_cap = 0;            // bytes
-    BufDesc* d_sdescs = nullptr;
-    size_t ds_cap = 0;            // bytes
+    PinBuf<uint8_t> h_stage;
+    size_t len = 0;
+    DevBuf<uint8_t> d_arena;
+    PinBuf<uint8_t> h_sched;      // pinned schedule (sorted descriptors, then ranges)
+    DevBuf<uint8_t> d_sched;
     std::vector<BufDesc> descs;   // this chunk: offset in the slot, global seq, .pad = global index
     hipEvent_t copied = nullptr;  // H2D of the chunk done: the host may refill h_stage
     hipEvent_t done = nullptr;    // kernel of the chunk done: the device may refill d_arena
@@ -288,47 +333,16 @@ struct nmg_engine {
   bool merge_timed = false;
   uint64_t merge_bytes = 0;  // counter bytes each worker contributes per merge
   std::vector<void*> comms;  // ncclComm_t per worker (distinct devices)
-  std::vector<uint8_t*> warena;
-  std::vector<size_t> warena_cap;
+  std::vector<DevBuf<uint8_t>> warena;  // each on its worker's device
 
   // partition-first path for large tables (nmg_route.h): the partitions of
   // the current table, and the per-analysis chunk pool
-  bool route_ok = false;          // partitions built for the current table
+  RouteTable rt;
   uint64_t route_launches = 0;    // analyses (or streamed chunks) that took the partition-first path
-  uint32_t nparts = 0;
-  PartInfo* d_parts = nullptr;
-  uint64_t* d_pbounds = nullptr;  // [kMaxParts + 1] partition starts, ascending
-  uint16_t* d_pdir = nullptr;     // [kRouteDir] the route pass's directory over them
-  uint32_t* d_pdead = nullptr;    // [(kMaxParts + 1) / 32] partitions no sample with ts != 0 can match
-  RSeg rsegs[kRouteSegs];         // its segments
+  RSeg rsegs[kRouteSegs];         // the route pass's directory segments
   uint64_t route_tbase = 0;       // compact records: timestamps relative to this (XLayout)
   uint32_t nrsegs = 0;
-  uint64_t* d_pe_keys = nullptr;  // [nparts][kPartSlots]
-  uint4* d_pe_nodes = nullptr;    // [nparts][kPartSlots][2]
-  uint4* d_pe_pnode = nullptr;    // [nparts][kPartSlots] packed node records (PackedNode)
-  uint4* d_pe_old = nullptr;      // [nparts][kOldLds] older entries, packed
-  uint32_t* d_pe_oinf = nullptr;  // [nparts][kOldLds]
-  uint2* d_pe_info = nullptr;     // [nparts][kPartSlots]
-  uint4* d_pe_dir = nullptr;      // [nparts][kPartDir] (PartDir)
-  uint32_t* d_pe_ids = nullptr;   // [table entries] entry id per table position (online tables; else null)
-  uint32_t* d_pe_lrel = nullptr;  // [table entries] first packed LDS cell (online tables)
-  uint32_t* d_pe_cmap = nullptr;  // packed cell -> histogram cell (online tables)
-  uint4* d_rec16 = nullptr;       // chunk pool: [chunks][kChunk] (addr, ts) and X words
-  uint32_t* d_cmeta = nullptr;
-  unsigned long long* d_cmatch = nullptr;
-  uint32_t* d_clist = nullptr;
-  size_t route_chunk_cap = 0;
-  uint4* d_items = nullptr;
-  size_t items_cap = 0;
-  uint32_t* d_chunk0 = nullptr;   // [grid + 1]
-  uint32_t* d_used = nullptr;     // [grid]
-  uint32_t* d_pcnt = nullptr;     // [grid][nparts]
-  uint32_t* d_pbase = nullptr;    // [nparts]
-  uint32_t* d_ctl = nullptr;      // [3] items, dequeue head, overflow records
-  uint4* d_ovf16 = nullptr;       // overflow list (route pass, pool exhausted)
-  unsigned long long* d_ovfx = nullptr;
-  size_t ovf_cap = 0;
-  size_t route_grid_cap = 0;
+  RoutePool rpool;
   bool sched_route = false;       // d_sdescs / d_ranges hold the analysis-order schedule
   uint32_t route_sched_key = 0;   // nparts (| tiny-pool switch) the pools were sized for
   bool route_pending = false;     // per-buffer match counts of the last route analysis not yet summed
@@ -336,8 +350,8 @@ struct nmg_engine {
   XLayout route_xl{};
 
   // kDbgTiming (internal): per-wave phase cycles of the last launch
-  uint64_t* d_dbg = nullptr;
-  size_t dbg_cap = 0, dbg_len = 0;
+  DevBuf<uint64_t> d_dbg;
+  size_t dbg_len = 0;
 };
 
 #define HIP_TRY(h, expr)                                                        \
@@ -348,21 +362,6 @@ struct nmg_engine {
       return NMG_ERR_HIP;                                                       \
     }                                                                           \
   } while (0)
-
-// The lookup structures' pointers and shape, moved out of the engine so that
-// a new table can be built beside them (nmg_update_objects swaps only on
-// success).
-struct LookupSet {
-  uint64_t* keys;
-  DevEntry* nodes;
-  uint64_t* efences;
-  DevEntry* enodes;
-  uint64_t* ffences;
-  uint8_t* fshift;
-  uint2* dir;
-  DevEntry* chain;
-  uint32_t K, elevels, nb_fences, fence_log2, dir_log2;
-};
 
 // a host copy into pinned staging, run by one of the copy threads
 struct CopyTask {
@@ -389,23 +388,26 @@ struct RouteJob {
 #pragma GCC visibility push(hidden)
 extern thread_local std::string g_create_error;  // detail of the last failed nmg_create (no handle holds it)
 int fail(nmg_engine* h, int code, const std::string& msg);
-void free_counters(nmg_engine* h);
-void free_lookup(nmg_engine* h);
-void free_route_table(nmg_engine* h);
-void snap_free(nmg_engine* h);  // the results snapshot's buffers and stream
 // an H2D copy of n bytes from host memory the caller may reuse at once:
 // through the pinned staging, on the engine stream, no host wait
 int stage_h2d(nmg_engine* h, void* d_dst, const void* src, size_t n);
 void stage_reset(nmg_engine* h);  // (an analysis' first upload: the staging from its start again)
-void free_route_pool(nmg_engine* h);
-LookupSet take_lookup(nmg_engine* h);
-void put_lookup(nmg_engine* h, const LookupSet& l);
-void free_table(nmg_engine* h);
-hipError_t alloc_copy(nmg_engine* h, void** dptr, const void* src, size_t bytes);
+void free_table(nmg_engine* h);  // the table's device structures: partitions, lookup, entries
+// b = n elements of src, uploaded on the engine stream (src is read until the stream is synchronised)
+template <class T>
+hipError_t alloc_copy(nmg_engine* h, DevBuf<T>& b, const T* src, size_t n) {
+  const hipError_t e = b.alloc(n);
+  if (e != hipSuccess || !n) return e;
+  return hipMemcpyAsync(b, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream);
+}
+template <class T>
+hipError_t alloc_copy(nmg_engine* h, DevBuf<T>& b, const std::vector<T>& src) {
+  return alloc_copy(h, b, src.data(), src.size());
+}
 int check_table(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
                        uint32_t n);
-int build_lookup(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
-                        const std::vector<DevEntry>& chain, DevEntry* chain_dev);
+int build_lookup(nmg_engine* h, LookupSet& l, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
+                 const std::vector<DevEntry>& chain, DevEntry* chain_dev);
 void route_segments(const uint64_t* b, uint32_t P, RSeg* seg, uint32_t* nseg, std::vector<uint16_t>& dir);
 int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t K,
                             const std::vector<DevEntry>& dev, const uint32_t* ids);
@@ -418,6 +420,7 @@ int check_buffer_args(nmg_engine* h, uint64_t len, uint32_t thread_rank, uint32_
 void run_copies(nmg_engine* h, const std::vector<CopyTask>& tasks);
 int slot_acquire(nmg_engine* h, int s);
 int ensure_bufcnt(nmg_engine* h, size_t need);
+int ensure_dbg(nmg_engine* h, size_t words);  // the timing buffer: `words` u64, zeroed on the engine stream
 int stream_flush(nmg_engine* h);
 int stream_dst(nmg_engine* h, uint64_t len, uint8_t** dst, std::vector<CopyTask>* pending);
 int stream_append(nmg_engine* h, uint64_t len, uint32_t thread_rank, uint32_t access);

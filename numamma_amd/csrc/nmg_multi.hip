@@ -57,8 +57,7 @@ int multi_create(nmg_engine* h, const nmg_options* opt) {
     if (rc) return fail(h, rc, "worker engine on device " + std::to_string(h->devices[i]) + ": " + g_create_error);
     h->workers.push_back(w);
   }
-  h->warena.assign(n, nullptr);
-  h->warena_cap.assign(n, 0);
+  h->warena.resize(n);
   h->multi = true;
   h->multi_distinct = all_distinct;
   if (all_distinct) {
@@ -77,7 +76,7 @@ void multi_destroy(nmg_engine* h) {
   for (size_t i = 0; i < h->workers.size(); i++) {
     if (h->warena[i]) {
       (void)hipSetDevice(h->workers[i]->device);
-      (void)hipFree(h->warena[i]);
+      h->warena[i].reset();
     }
   }
   if (Rccl* r = rccl())
@@ -130,12 +129,9 @@ int multi_analyze(nmg_engine* h) {
     HIP_TRY(h, hipSetDevice(w->device));
     int rc = NMG_OK;
     if (stage) {
-      if (span + 64 > h->warena_cap[i]) {
+      if (span + 64 > h->warena[i].cap()) {
         HIP_TRY(h, hipStreamSynchronize(w->stream));
-        (void)hipFree(h->warena[i]);
-        h->warena[i] = nullptr;
-        h->warena_cap[i] = span + 64;
-        HIP_TRY(h, hipMalloc(&h->warena[i], h->warena_cap[i]));
+        HIP_TRY(h, h->warena[i].reserve(span + 64));
       }
       if (span) HIP_TRY(h, hipMemcpyAsync(h->warena[i], h->h_stage + base, span, hipMemcpyHostToDevice, w->stream));
       rc = nmg_set_device_buffers(w, h->warena[i], offs.data(), lens.data(), ranks.data(), acc.data(), b - a, a);
@@ -271,7 +267,7 @@ int multi_finish(nmg_engine* h) {
     vals.insert(vals.end(), v0.begin(), v0.end());
   }
   HIP_TRY(h, hipSetDevice(h->device));
-  if (h->d_sparse_keys) {
+  if (h->cnt.d_sparse_keys) {
     std::vector<size_t> ord(keys.size());
     for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return keys[a] < keys[b]; });

@@ -33,7 +33,7 @@ bool route_layout(nmg_engine* h, const std::vector<BufDesc>& descs, XLayout& xl)
 bool route_eligible(nmg_engine* h, const std::vector<BufDesc>& descs) {
   constexpr uint32_t kLegacyOnly = kDbgLoadOnly | kDbgNoGlobal | kDbgNoFlush | kDbgNoTables | kDbgTiming |
                                    kDbgTinyLog | kDbgNoPack | kDbgNoDir | kDbgNoRoute | NMG_F_SINGLE_PASS;
-  if (!h->route_ok || (h->flags & kLegacyOnly) || descs.empty()) return false;
+  if (!h->rt.ok || (h->flags & kLegacyOnly) || descs.empty()) return false;
   // the first-match ordinal is rebuilt from the buffer index: seq = seq0 + index
   uint64_t bytes = 0;
   for (size_t i = 0; i < descs.size(); i++) {
@@ -41,7 +41,7 @@ bool route_eligible(nmg_engine* h, const std::vector<BufDesc>& descs) {
     bytes += descs[i].len;
   }
   // chunk ids (route pass LDS: id << 7 | fill) -- an upper bound of the pool
-  const uint64_t chunks = (bytes / kRecBytes + descs.size()) / kChunk + (uint64_t)h->num_cus * (2 * h->nparts + 2);
+  const uint64_t chunks = (bytes / kRecBytes + descs.size()) / kChunk + (uint64_t)h->num_cus * (2 * h->rt.nparts + 2);
   if (chunks >= (1ull << kChunkIdBits)) return false;
   XLayout xl;
   return route_layout(h, descs, xl);
@@ -53,7 +53,7 @@ bool route_eligible(nmg_engine* h) { return route_eligible(h, h->descs); }
 // next chunks); shorter records past that are attributed directly
 int route_pool(nmg_engine* h, const std::vector<BufDesc>& descs, uint32_t grid, const uint32_t* ranges,
                       std::vector<uint32_t>& c0) {
-  const uint32_t P = h->nparts;
+  const uint32_t P = h->rt.nparts;
   c0.assign(grid + 1, 0);
   uint64_t tot = 0;
   for (uint32_t w = 0; w < grid; w++) {
@@ -74,29 +74,24 @@ int route_pool(nmg_engine* h, const std::vector<BufDesc>& descs, uint32_t grid, 
   for (const BufDesc& d : descs) recs += (d.len + kRecBytes - 1) / kRecBytes;
   // (a quarter of the records, plus up to three times them for batches under 4M records)
   const size_t ovf = (size_t)((h->flags & kDbgTinyPool) ? recs : recs / 4 + std::min<uint64_t>(3 * recs, 4u << 20)) + 65536;
-  if (tot > h->route_chunk_cap || items > h->items_cap || grid > h->route_grid_cap || ovf > h->ovf_cap) {
+  RoutePool& rp = h->rpool;
+  if (tot > rp.d_cmeta.cap() || items > rp.d_items.cap() || grid > rp.d_used.cap() || ovf > rp.d_ovfx.cap()) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // a launch in flight may still read the old pool
-    const bool pending = h->route_pending;
-    free_route_pool(h);
-    h->route_pending = pending;
+    rp = RoutePool();  // (the whole pool anew, sized together; route_pending is kept)
     const size_t cap = std::max<size_t>(tot, 1);
-    HIP_TRY(h, hipMalloc(&h->d_rec16, cap * kChunk * sizeof(uint4)));
-    HIP_TRY(h, hipMalloc(&h->d_cmeta, cap * 4));
-    HIP_TRY(h, hipMalloc(&h->d_cmatch, cap * 8));
-    HIP_TRY(h, hipMalloc(&h->d_clist, cap * 4));
-    HIP_TRY(h, hipMalloc(&h->d_items, items * sizeof(uint4)));
-    HIP_TRY(h, hipMalloc(&h->d_chunk0, (grid + 1) * 4));
-    HIP_TRY(h, hipMalloc(&h->d_used, grid * 4));
-    HIP_TRY(h, hipMalloc(&h->d_pcnt, (size_t)grid * (kMaxParts + 1) * 4));
-    HIP_TRY(h, hipMalloc(&h->d_pbase, (kMaxParts + 1) * 4));
-    HIP_TRY(h, hipMalloc(&h->d_ctl, 4 * 4));
-    HIP_TRY(h, hipMemset(h->d_ctl, 0, 4 * 4));
-    HIP_TRY(h, hipMalloc(&h->d_ovf16, ovf * sizeof(uint4)));
-    HIP_TRY(h, hipMalloc(&h->d_ovfx, ovf * 8));
-    h->ovf_cap = ovf;
-    h->route_chunk_cap = cap;
-    h->items_cap = items;
-    h->route_grid_cap = grid;
+    HIP_TRY(h, rp.d_rec16.alloc(cap * kChunk));
+    HIP_TRY(h, rp.d_cmeta.alloc(cap));
+    HIP_TRY(h, rp.d_cmatch.alloc(cap));
+    HIP_TRY(h, rp.d_clist.alloc(cap));
+    HIP_TRY(h, rp.d_items.alloc(items));
+    HIP_TRY(h, rp.d_chunk0.alloc(grid + 1));
+    HIP_TRY(h, rp.d_used.alloc(grid));
+    HIP_TRY(h, rp.d_pcnt.alloc((size_t)grid * (kMaxParts + 1)));
+    HIP_TRY(h, rp.d_pbase.alloc(kMaxParts + 1));
+    HIP_TRY(h, rp.d_ctl.alloc(4));
+    HIP_TRY(h, hipMemset(rp.d_ctl, 0, 4 * 4));
+    HIP_TRY(h, rp.d_ovf16.alloc(ovf));
+    HIP_TRY(h, rp.d_ovfx.alloc(ovf));
   }
   return NMG_OK;
 }
@@ -105,9 +100,9 @@ int route_prepare(nmg_engine* h, uint32_t grid, const std::vector<uint32_t>& ran
   std::vector<uint32_t> c0;
   const int rc = route_pool(h, h->descs, grid, ranges.data(), c0);
   if (rc) return rc;
-  const int rc2 = stage_h2d(h, h->d_chunk0, c0.data(), (grid + 1) * 4);
+  const int rc2 = stage_h2d(h, h->rpool.d_chunk0, c0.data(), (grid + 1) * 4);
   if (rc2) return rc2;
-  h->route_sched_key = h->nparts | ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u);
+  h->route_sched_key = h->rt.nparts | ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u);
   return NMG_OK;
 }
 
@@ -116,7 +111,7 @@ int route_prepare(nmg_engine* h, uint32_t grid, const std::vector<uint32_t>& ran
 // (analysis order), bracketed by the launch-timing events.
 int route_analyze(nmg_engine* h, uint32_t nb, uint32_t grid) {
   (void)nb;
-  RouteJob job{&h->descs, h->d_data, h->d_sdescs, h->d_ranges, h->d_chunk0, grid, 0, false};
+  RouteJob job{&h->descs, h->d_data, h->d_sdescs, h->d_ranges, h->rpool.d_chunk0, grid, 0, false};
   return route_analyze_job(h, job);
 }
 
@@ -136,95 +131,81 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
   RouteParams rp;
   memset(&rp, 0, sizeof(rp));
   rp.p = base;
-  rp.pbounds = h->d_pbounds;
-  rp.pdir = h->d_pdir;
-  rp.pdead = h->d_pdead;
+  rp.pbounds = h->rt.d_pbounds;
+  rp.pdir = h->rt.d_pdir;
+  rp.pdead = h->rt.d_pdead;
   for (uint32_t k = 0; k < kRouteSegs; k++) rp.seg[k] = h->rsegs[k];
   rp.nseg = h->nrsegs;
-  rp.nparts = h->nparts;
+  rp.nparts = h->rt.nparts;
   rp.xl = xl;
   rp.seq0 = seq0;
-  rp.rec16 = h->d_rec16;
-  rp.cmeta = h->d_cmeta;
+  rp.rec16 = h->rpool.d_rec16;
+  rp.cmeta = h->rpool.d_cmeta;
   rp.chunk0 = job.chunk0;
-  rp.used = h->d_used;
-  rp.ovf16 = h->d_ovf16;
-  rp.ovfx = h->d_ovfx;
-  rp.ovf_cnt = h->d_ctl + 2;
-  rp.ovf_cap = (uint32_t)std::min<size_t>(h->ovf_cap, 0xffffffffu);
+  rp.used = h->rpool.d_used;
+  rp.ovf16 = h->rpool.d_ovf16;
+  rp.ovfx = h->rpool.d_ovfx;
+  rp.ovf_cnt = h->rpool.d_ctl + 2;
+  rp.ovf_cap = (uint32_t)std::min<size_t>(h->rpool.d_ovfx.cap(), 0xffffffffu);
   if (h->flags & kDbgTinyOvf) rp.ovf_cap = std::min<uint32_t>(rp.ovf_cap, 64);  // (tests: the direct attribution past a full list)
   if (h->flags & kDbgRouteTiming) {  // (internal) per-wave phase cycles, read by nmg_debug_timing
-    const size_t n = (size_t)grid * (kWG / 64) * kRouteTimingWords;
-    if (n > h->dbg_cap) {
-      (void)hipFree(h->d_dbg);
-      h->d_dbg = nullptr;
-      HIP_TRY(h, hipMalloc(&h->d_dbg, n * 8));
-      h->dbg_cap = n;
-    }
-    HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, n * 8, h->stream));
-    h->dbg_len = n;
-    rp.p.dbg = reinterpret_cast<unsigned long long*>(h->d_dbg);
+    rc = ensure_dbg(h, (size_t)grid * (kWG / 64) * kRouteTimingWords);
+    if (rc) return rc;
+    rp.p.dbg = reinterpret_cast<unsigned long long*>(h->d_dbg.get());
   }
   HIP_TRY(h, launch_route(grid, h->stream, rp));
   HIP_TRY(h, hipEventRecord(h->ringr[slot], h->stream));
   HIP_TRY(h, launch_overflow(h->stream, rp));
   ScatterParams sc;
-  sc.cmeta = h->d_cmeta;
+  sc.cmeta = h->rpool.d_cmeta;
   sc.chunk0 = job.chunk0;
-  sc.used = h->d_used;
-  sc.pcnt = h->d_pcnt;
-  sc.pbase = h->d_pbase;
-  sc.clist = h->d_clist;
-  sc.nparts = h->nparts;
+  sc.used = h->rpool.d_used;
+  sc.pcnt = h->rpool.d_pcnt;
+  sc.pbase = h->rpool.d_pbase;
+  sc.clist = h->rpool.d_clist;
+  sc.nparts = h->rt.nparts;
   CountParams cp;
   memset(&cp, 0, sizeof(cp));
   cp.sc = sc;
   HIP_TRY(h, launch_count(grid, h->stream, cp));
   PlanParams pl;
-  pl.pcnt = h->d_pcnt;
-  pl.pbase = h->d_pbase;
-  pl.items = h->d_items;
-  pl.ctl = h->d_ctl;
+  pl.pcnt = h->rpool.d_pcnt;
+  pl.pbase = h->rpool.d_pbase;
+  pl.items = h->rpool.d_items;
+  pl.ctl = h->rpool.d_ctl;
   pl.grid = grid;
-  pl.nparts = h->nparts;
+  pl.nparts = h->rt.nparts;
   HIP_TRY(h, launch_plan(h->stream, pl));
   HIP_TRY(h, launch_scatter(grid, h->stream, sc));
   LocalParams lp;
   memset(&lp, 0, sizeof(lp));
   lp.p = base;
-  lp.parts = h->d_parts;
-  lp.pe_keys = h->d_pe_keys;
-  lp.pe_nodes = h->d_pe_nodes;
-  lp.pe_info = h->d_pe_info;
-  lp.pe_pnode = h->d_pe_pnode;
-  lp.pe_old = h->d_pe_old;
-  lp.pe_oinf = h->d_pe_oinf;
-  lp.pe_dir = h->d_pe_dir;
-  lp.pe_ids = h->d_pe_ids;
-  lp.pe_lrel = h->d_pe_lrel;
-  lp.pe_cmap = h->d_pe_cmap;
-  lp.rec16 = h->d_rec16;
-  lp.cmeta = h->d_cmeta;
-  lp.clist = h->d_clist;
-  lp.items = h->d_items;
-  lp.ctl = h->d_ctl;
-  lp.cmatch = h->d_cmatch;
+  lp.parts = h->rt.d_parts;
+  lp.pe_keys = h->rt.d_pe_keys;
+  lp.pe_nodes = h->rt.d_pe_nodes;
+  lp.pe_info = h->rt.d_pe_info;
+  lp.pe_pnode = h->rt.d_pe_pnode;
+  lp.pe_old = h->rt.d_pe_old;
+  lp.pe_oinf = h->rt.d_pe_oinf;
+  lp.pe_dir = h->rt.d_pe_dir;
+  lp.pe_ids = h->rt.d_pe_ids;
+  lp.pe_lrel = h->rt.d_pe_lrel;
+  lp.pe_cmap = h->rt.d_pe_cmap;
+  lp.rec16 = h->rpool.d_rec16;
+  lp.cmeta = h->rpool.d_cmeta;
+  lp.clist = h->rpool.d_clist;
+  lp.items = h->rpool.d_items;
+  lp.ctl = h->rpool.d_ctl;
+  lp.cmatch = h->rpool.d_cmatch;
   lp.descs = job.sdescs;
   lp.xl = xl;
   lp.seq0 = seq0;
   lp.fresh = h->counters_fresh ? 1u : 0u;
   h->counters_fresh = false;
   if ((h->flags & kDbgLocalTiming) && !(h->flags & kDbgRouteTiming)) {  // (internal) per-wave phase cycles
-    const size_t n = (size_t)h->num_cus * (kWG / 64) * kRouteTimingWords;
-    if (n > h->dbg_cap) {
-      (void)hipFree(h->d_dbg);
-      h->d_dbg = nullptr;
-      HIP_TRY(h, hipMalloc(&h->d_dbg, n * 8));
-      h->dbg_cap = n;
-    }
-    HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, n * 8, h->stream));
-    h->dbg_len = n;
-    lp.p.dbg = reinterpret_cast<unsigned long long*>(h->d_dbg);
+    rc = ensure_dbg(h, (size_t)h->num_cus * (kWG / 64) * kRouteTimingWords);
+    if (rc) return rc;
+    lp.p.dbg = reinterpret_cast<unsigned long long*>(h->d_dbg.get());
   }
   HIP_TRY(h, launch_local((uint32_t)h->num_cus, h->stream, lp));
   HIP_TRY(h, hipEventRecord(h->ringm[slot], h->stream));
@@ -235,10 +216,10 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
     FoundParams f;
     f.ranges = job.ranges;
     f.chunk0 = job.chunk0;
-    f.used = h->d_used;
-    f.cmeta = h->d_cmeta;
-    f.cmatch = h->d_cmatch;
-    f.rec16 = h->d_rec16;
+    f.used = h->rpool.d_used;
+    f.cmeta = h->rpool.d_cmeta;
+    f.cmatch = h->rpool.d_cmatch;
+    f.rec16 = h->rpool.d_rec16;
     f.bufcnt = h->d_bufcnt + job.index_base;
     f.nb_bufs = (uint32_t)h->bufcnt_stride;
     f.gbits = xl.gbits;
@@ -260,11 +241,11 @@ int route_settle(nmg_engine* h) {
   h->route_pending = false;
   FoundParams f;
   f.ranges = h->d_ranges;
-  f.chunk0 = h->d_chunk0;
-  f.used = h->d_used;
-  f.cmeta = h->d_cmeta;
-  f.cmatch = h->d_cmatch;
-  f.rec16 = h->d_rec16;
+  f.chunk0 = h->rpool.d_chunk0;
+  f.used = h->rpool.d_used;
+  f.cmeta = h->rpool.d_cmeta;
+  f.cmatch = h->rpool.d_cmatch;
+  f.rec16 = h->rpool.d_rec16;
   f.bufcnt = h->d_bufcnt;
   f.nb_bufs = (uint32_t)h->bufcnt_stride;
   f.gbits = h->route_xl.gbits;

@@ -5,18 +5,13 @@
 #include "nmg_engine_impl.h"
 
 int stage_reserve(nmg_engine* h, size_t need) {
-  if (need <= h->stage_cap) return NMG_OK;
-  size_t cap = std::max(need, h->stage_cap * 2 + (1u << 20));
-  uint8_t* p = nullptr;
+  if (need <= h->h_stage.cap()) return NMG_OK;
   // (portable: a multi-GPU engine's workers copy from it on every device)
-  HIP_TRY(h, hipHostMalloc((void**)&p, cap, h->multi ? hipHostMallocPortable : hipHostMallocDefault));
+  PinBuf<uint8_t> p(h->multi ? PinMem::portable() : PinMem());
+  HIP_TRY(h, p.alloc(std::max(need, h->h_stage.cap() * 2 + (1u << 20))));
   if (h->stage_len) memcpy(p, h->h_stage, h->stage_len);
-  if (h->h_stage) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    (void)hipHostFree(h->h_stage);
-  }
-  h->h_stage = p;
-  h->stage_cap = cap;
+  if (h->h_stage) HIP_TRY(h, hipStreamSynchronize(h->stream));  // (an upload may still read the old block)
+  h->h_stage = std::move(p);
   return NMG_OK;
 }
 
@@ -217,15 +212,16 @@ int slot_acquire(nmg_engine* h, int s) {
 // chunks are in flight (grown by doubling after draining the engine stream)
 int ensure_bufcnt(nmg_engine* h, size_t need) {
   if (need <= h->bufcnt_stride) return NMG_OK;
-  if (h->bufcnt_stride == 0 && need <= h->bufcnt_cap) {  // a kept array, first chunk
-    h->bufcnt_stride = h->bufcnt_cap;
-    HIP_TRY(h, hipMemsetAsync(h->d_bufcnt, 0, h->bufcnt_cap * 2 * 4, h->stream));
+  const size_t old_cap = h->d_bufcnt.cap() / 2;
+  if (h->bufcnt_stride == 0 && need <= old_cap) {  // a kept array, first chunk
+    h->bufcnt_stride = old_cap;
+    HIP_TRY(h, hipMemsetAsync(h->d_bufcnt, 0, old_cap * 2 * 4, h->stream));
     return NMG_OK;
   }
-  const size_t cap = std::max<size_t>({need, h->bufcnt_cap * 2, (size_t)4096});
-  uint32_t* nb = nullptr;
+  const size_t cap = std::max<size_t>({need, old_cap * 2, (size_t)4096});
+  DevBuf<uint32_t> nb;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMalloc(&nb, cap * 2 * 4));
+  HIP_TRY(h, nb.alloc(cap * 2));
   HIP_TRY(h, hipMemsetAsync(nb, 0, cap * 2 * 4, h->stream));
   if (h->d_bufcnt && h->bufcnt_stride) {
     HIP_TRY(h, hipMemcpyAsync(nb, h->d_bufcnt, h->bufcnt_stride * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -233,9 +229,7 @@ int ensure_bufcnt(nmg_engine* h, size_t need) {
                               hipMemcpyDeviceToDevice, h->stream));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  (void)hipFree(h->d_bufcnt);
-  h->d_bufcnt = nb;
-  h->bufcnt_cap = cap;
+  h->d_bufcnt = std::move(nb);
   h->bufcnt_stride = cap;
   return NMG_OK;
 }
@@ -256,47 +250,35 @@ int stream_flush(nmg_engine* h) {
   // schedule, then the ranges and the workgroups' chunk pools)
   const bool route = route_eligible(h, sl.descs);
   const size_t sched_bytes = nb * sizeof(BufDesc) + (grid + 1) * 4 * (route ? 2 : 1);
-  if (sched_bytes > sl.hs_cap) {  // (slot acquired: its previous H2D is done)
-    if (sl.h_sdescs) (void)hipHostFree(sl.h_sdescs);
-    sl.h_sdescs = nullptr;
-    sl.hs_cap = std::max<size_t>(sched_bytes * 2, 64 << 10);
-    HIP_TRY(h, hipHostMalloc((void**)&sl.h_sdescs, sl.hs_cap, hipHostMallocDefault));
-  }
+  if (sched_bytes > sl.h_sched.cap())  // (slot acquired: its previous H2D is done)
+    HIP_TRY(h, sl.h_sched.reserve(std::max<size_t>(sched_bytes * 2, 64 << 10)));
   const uint32_t index_base = (uint32_t)(h->descs.size() - nb);
-  uint32_t* h_ranges = reinterpret_cast<uint32_t*>(sl.h_sdescs + nb);
-  make_schedule(sl.descs, grid, index_base, sl.h_sdescs, h_ranges, !route);
+  BufDesc* h_sdescs = reinterpret_cast<BufDesc*>(sl.h_sched.get());
+  uint32_t* h_ranges = reinterpret_cast<uint32_t*>(h_sdescs + nb);
+  make_schedule(sl.descs, grid, index_base, h_sdescs, h_ranges, !route);
   if (route) {
     std::vector<uint32_t> c0;
     rc = route_pool(h, sl.descs, grid, h_ranges, c0);  // (may wait for the stream to grow the pool)
     if (rc) return rc;
     memcpy(h_ranges + grid + 1, c0.data(), (grid + 1) * 4);
   }
-  if (sl.len + 64 > sl.dcap || sched_bytes > sl.ds_cap) {  // grow the device side: wait for its last kernel
+  if (sl.len + 64 > sl.d_arena.cap() || sched_bytes > sl.d_sched.cap()) {  // grow the device side: wait for its last kernel
     if (sl.used) HIP_TRY(h, hipEventSynchronize(sl.done));
-    if (sl.len + 64 > sl.dcap) {
-      (void)hipFree(sl.d_arena);
-      sl.d_arena = nullptr;
-      sl.dcap = std::max<size_t>(sl.len + 64, sl.cap + 64);
-      HIP_TRY(h, hipMalloc(&sl.d_arena, sl.dcap));
-    }
-    if (sched_bytes > sl.ds_cap) {
-      (void)hipFree(sl.d_sdescs);
-      sl.d_sdescs = nullptr;
-      sl.ds_cap = sl.hs_cap;
-      HIP_TRY(h, hipMalloc(&sl.d_sdescs, sl.ds_cap));
-    }
+    if (sl.len + 64 > sl.d_arena.cap()) HIP_TRY(h, sl.d_arena.reserve(std::max<size_t>(sl.len + 64, sl.h_stage.cap() + 64)));
+    if (sched_bytes > sl.d_sched.cap()) HIP_TRY(h, sl.d_sched.reserve(sl.h_sched.cap()));
   }
   if (sl.used) HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, sl.done, 0));
   HIP_TRY(h, hipMemcpyAsync(sl.d_arena, sl.h_stage, sl.len, hipMemcpyHostToDevice, h->copy_stream));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_sdescs, sl.h_sdescs, sched_bytes, hipMemcpyHostToDevice, h->copy_stream));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_sched, sl.h_sched, sched_bytes, hipMemcpyHostToDevice, h->copy_stream));
   HIP_TRY(h, hipEventRecord(sl.copied, h->copy_stream));
   HIP_TRY(h, hipStreamWaitEvent(h->stream, sl.copied, 0));
-  const uint32_t* d_ranges = reinterpret_cast<const uint32_t*>(sl.d_sdescs + nb);
+  const BufDesc* d_sdescs = reinterpret_cast<const BufDesc*>(sl.d_sched.get());
+  const uint32_t* d_ranges = reinterpret_cast<const uint32_t*>(d_sdescs + nb);
   if (route) {
-    const RouteJob job{&sl.descs, sl.d_arena, sl.d_sdescs, d_ranges, d_ranges + grid + 1, grid, index_base, true};
+    const RouteJob job{&sl.descs, sl.d_arena, d_sdescs, d_ranges, d_ranges + grid + 1, grid, index_base, true};
     rc = route_analyze_job(h, job);
   } else {
-    rc = launch_attribution(h, sl.d_arena, sl.d_sdescs, d_ranges, nb, grid, sl.len);
+    rc = launch_attribution(h, sl.d_arena, d_sdescs, d_ranges, nb, grid, sl.len);
   }
   if (rc) return rc;
   HIP_TRY(h, hipEventRecord(sl.done, h->stream));
@@ -319,10 +301,9 @@ int stream_dst(nmg_engine* h, uint64_t len, uint8_t** dst, std::vector<CopyTask>
     if (rc) return rc;
     sl = &h->slots[h->cur_slot];
   }
-  if (sl->len + len + 16 > sl->cap) {  // first use, or one buffer larger than a chunk
-    const size_t cap = std::max<size_t>(h->chunk_cap, sl->len + len + 16);
-    uint8_t* p = nullptr;
-    HIP_TRY(h, hipHostMalloc((void**)&p, cap, hipHostMallocDefault));
+  if (sl->len + len + 16 > sl->h_stage.cap()) {  // first use, or one buffer larger than a chunk
+    PinBuf<uint8_t> p;
+    HIP_TRY(h, p.alloc(std::max<size_t>(h->chunk_cap, sl->len + len + 16)));
     if (sl->len) {
       if (pending) {  // pending copies target the old block
         run_copies(h, *pending);
@@ -330,9 +311,7 @@ int stream_dst(nmg_engine* h, uint64_t len, uint8_t** dst, std::vector<CopyTask>
       }
       memcpy(p, sl->h_stage, sl->len);
     }
-    if (sl->h_stage) (void)hipHostFree(sl->h_stage);
-    sl->h_stage = p;
-    sl->cap = cap;
+    sl->h_stage = std::move(p);
   }
   *dst = sl->h_stage + sl->len;
   return NMG_OK;
@@ -498,17 +477,10 @@ extern "C" int nmg_clear_buffers(nmg_engine* h) {
 int stage_h2d(nmg_engine* h, void* d_dst, const void* src, size_t n) {
   if (!n) return NMG_OK;
   const size_t need = (n + 255) & ~size_t(255);
-  if (h->up_off + need > h->up_cap) {  // full: every copy from it done first, then from its start
+  if (h->up_off + need > h->up_pin.cap()) {  // full: every copy from it done first, then from its start
     if (h->up_recorded) HIP_TRY(h, hipEventSynchronize(h->up_ev));
     h->up_off = 0;
-    if (need > h->up_cap) {
-      (void)hipHostFree(h->up_pin);
-      h->up_pin = nullptr;
-      h->up_cap = 0;
-      const size_t cap = std::max<size_t>(need * 2, 4u << 20);
-      HIP_TRY(h, hipHostMalloc((void**)&h->up_pin, cap, 0));
-      h->up_cap = cap;
-    }
+    if (need > h->up_pin.cap()) HIP_TRY(h, h->up_pin.reserve(std::max<size_t>(need * 2, 4u << 20)));
   }
   if (!h->up_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->up_ev, hipEventDisableTiming));
   uint8_t* p = h->up_pin + h->up_off;
@@ -530,12 +502,9 @@ void stage_reset(nmg_engine* h) {
 int upload_buffers(nmg_engine* h) {
   Range range("nmg_stage_h2d");
   if (!h->external && h->staged_dirty) {
-    if (h->stage_len + 64 > h->arena_cap) {
+    if (h->stage_len + 64 > h->d_arena.cap()) {
       HIP_TRY(h, hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_arena);
-      h->d_arena = nullptr;
-      h->arena_cap = h->stage_len + 64;
-      HIP_TRY(h, hipMalloc(&h->d_arena, h->arena_cap));
+      HIP_TRY(h, h->d_arena.reserve(h->stage_len + 64));
     }
     if (h->stage_len) HIP_TRY(h, hipMemcpyAsync(h->d_arena, h->h_stage, h->stage_len, hipMemcpyHostToDevice, h->stream));
     h->d_data = h->d_arena;
@@ -546,16 +515,11 @@ int upload_buffers(nmg_engine* h) {
     // in-place buffers: offsets against the arena base (u64 arithmetic, as the kernels' data + offset)
     for (size_t i = 0; i < h->zc_dev.size() && i < n; i++)
       if (h->zc_dev[i]) h->descs[i].offset = h->zc_dev[i] - (uint64_t)(uintptr_t)h->d_data;
-    if (n > h->descs_cap) {
+    if (n > h->d_descs.cap()) {  // (the per-buffer counts with them, sized alike)
       HIP_TRY(h, hipStreamSynchronize(h->stream));
-      (void)hipFree(h->d_descs);
-      (void)hipFree(h->d_bufcnt);
-      h->d_descs = nullptr;
-      h->d_bufcnt = nullptr;
-      h->descs_cap = n;
-      h->bufcnt_cap = n;
-      HIP_TRY(h, hipMalloc(&h->d_descs, n * sizeof(BufDesc)));
-      HIP_TRY(h, hipMalloc(&h->d_bufcnt, n * 2 * 4));
+      h->d_bufcnt.reset();
+      HIP_TRY(h, h->d_descs.alloc(n));
+      HIP_TRY(h, h->d_bufcnt.alloc(n * 2));
     }
     h->bufcnt_stride = n;
     if (n) {
@@ -608,16 +572,11 @@ int build_schedule(nmg_engine* h, uint32_t grid, bool by_stream) {
   std::vector<uint32_t> ranges(grid + 1, 0);
   std::vector<BufDesc> sorted(nb);
   make_schedule(h->descs, grid, 0, sorted.data(), ranges.data(), by_stream);
-  if (nb > h->sdescs_cap || grid + 1 > h->ranges_cap || !h->d_sdescs) {  // (grown only: a free waits for the device)
+  if (nb > h->d_sdescs.cap() || grid + 1 > h->d_ranges.cap()) {  // (grown only: a free waits for the device)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_sdescs);
-    (void)hipFree(h->d_ranges);
-    h->d_sdescs = nullptr;
-    h->d_ranges = nullptr;
-    h->sdescs_cap = std::max<size_t>(nb, 1);
-    h->ranges_cap = grid + 1;
-    HIP_TRY(h, hipMalloc(&h->d_sdescs, h->sdescs_cap * sizeof(BufDesc)));
-    HIP_TRY(h, hipMalloc(&h->d_ranges, h->ranges_cap * 4));
+    h->d_ranges.reset();
+    HIP_TRY(h, h->d_sdescs.alloc(std::max<size_t>(nb, 1)));
+    HIP_TRY(h, h->d_ranges.alloc(grid + 1));
   }
   int rc = stage_h2d(h, h->d_sdescs, sorted.data(), nb * sizeof(BufDesc));
   if (!rc) rc = stage_h2d(h, h->d_ranges, ranges.data(), (grid + 1) * 4);
@@ -651,35 +610,35 @@ Params base_params(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, co
   p.sbufs = sdescs;
   p.ranges = ranges;
   p.nb_bufs = (uint32_t)h->bufcnt_stride;
-  p.nb_keys = h->K;
-  p.keys = h->d_keys;
-  p.nodes = h->d_nodes;
+  p.nb_keys = h->lk.K;
+  p.keys = h->lk.keys;
+  p.nodes = h->lk.nodes;
   p.entries = h->d_entries;
-  p.chain = h->d_chain;
-  p.ffences = h->d_ffences;
-  p.fshift = h->d_fshift;
-  p.dir = h->d_dir;
-  p.nb_fences = h->nb_fences;
-  p.fence_log2 = h->fence_log2;
-  p.dir_log2 = h->dir_log2;
+  p.chain = h->lk.chain;
+  p.ffences = h->lk.ffences;
+  p.fshift = h->lk.fshift;
+  p.dir = h->lk.dir;
+  p.nb_fences = h->lk.nb_fences;
+  p.fence_log2 = h->lk.fence_log2;
+  p.dir_log2 = h->lk.dir_log2;
   p.nb_threads = h->T;
   p.flags = h->flags;
   p.nb_entries = h->E;
-  p.lds_nodes = h->K <= kLdsNodes;
-  p.elevels = h->elevels;
-  p.efences = h->d_efences;
-  p.enodes = h->d_enodes;
+  p.lds_nodes = h->lk.K <= kLdsNodes;
+  p.elevels = h->lk.elevels;
+  p.efences = h->lk.efences;
+  p.enodes = h->lk.enodes;
   p.sparse_mask = (uint32_t)(h->sparse_cap - 1);
   p.hist_cells = h->hist_cells;
-  p.sum64 = h->d_sum64;
-  p.min64 = h->d_min64;
-  p.max64 = h->d_max64;
-  p.hist = h->d_hist;
+  p.sum64 = h->cnt.d_sum64;
+  p.min64 = h->cnt.d_min64;
+  p.max64 = h->cnt.d_max64;
+  p.hist = h->cnt.d_hist;
   p.bufcnt = h->d_bufcnt;
   p.found = h->d_found;
-  p.sparse_keys = h->d_sparse_keys;
-  p.sparse_vals = h->d_sparse_vals;
-  p.sparse_dirty = h->d_sparse_dirty ? h->d_sparse_dirty + (h->nreset & 1) : nullptr;
+  p.sparse_keys = h->cnt.d_sparse_keys;
+  p.sparse_vals = h->cnt.d_sparse_vals;
+  p.sparse_dirty = h->cnt.d_sparse_dirty ? h->cnt.d_sparse_dirty + (h->nreset & 1) : nullptr;
   p.smatch = (h->flags & NMG_F_SAMPLE_MATCHES) ? h->d_smatch : nullptr;
   return p;
 }
@@ -697,6 +656,13 @@ int launch_events(nmg_engine* h, int* slot_out) {
   return NMG_OK;
 }
 
+int ensure_dbg(nmg_engine* h, size_t words) {
+  HIP_TRY(h, h->d_dbg.reserve(words));
+  HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, words * 8, h->stream));
+  h->dbg_len = words;
+  return NMG_OK;
+}
+
 int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, const uint32_t* ranges,
                               uint32_t nb, uint32_t grid, uint64_t nbytes) {
   Range range("nmg_attribute");
@@ -705,14 +671,14 @@ int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs
   // large tables: their own kernel instances (fences + directory + node records)
   const int mode = (h->E <= kObjSlots ? kModeDenseObj : 0) | (h->hist_cells <= kDensePageCells ? kModeDensePage : 0) |
                    (p.lds_nodes ? 0 : kModeLarge);
-  if (!(mode & kModeDenseObj) && h->d_pk64 && !(h->flags & kDbgNoPack)) {
+  if (!(mode & kModeDenseObj) && h->cnt.d_pk64 && !(h->flags & kDbgNoPack)) {
     // < 2^cbits packed samples in this launch (only SAMPLE records of at
     // least 40 B are packed: the kernel keeps shorter ones, which the
     // reference's byte cursor accepts, on the plain path); packed weights
     // < 2^(64 - 2 cbits), so any entry's packed sum < 2^(64 - cbits)
     const uint32_t cbits = 64 - (uint32_t)__builtin_clzll(nbytes / kRecBytes + 1);
     if (2 * cbits < 64) {
-      p.pk64 = h->d_pk64;
+      p.pk64 = h->cnt.d_pk64;
       p.pk_shift = 64 - cbits;
       p.pk_wlim = 1ull << (64 - 2 * cbits);
     }
@@ -727,26 +693,14 @@ int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs
     const uint64_t cap = (h->flags & kDbgTinyLog)
                              ? 2
                              : std::min<uint64_t>(1u << 20, (nbytes / kRecBytes) / ((uint64_t)grid * parts) * 5 / 4 + 32);
-    const size_t need = (size_t)grid * parts * cap * sizeof(uint4);  // (16 B slots; flushed slots take two)
-    if (need > h->tlog_bytes || (size_t)grid * parts > h->tlog_cnt_cap) {
+    const size_t logs = (size_t)grid * parts, need = logs * cap;  // (16 B slots; flushed slots take two)
+    if (need > h->cnt.d_tlog.cap() || logs > h->cnt.d_tlog_cnt.cap()) {
       HIP_TRY(h, hipStreamSynchronize(h->stream));  // an earlier launch may still read the old log
-      if (need > h->tlog_bytes) {
-        (void)hipFree(h->d_tlog);
-        h->d_tlog = nullptr;
-        h->tlog_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_tlog, need));
-        h->tlog_bytes = need;
-      }
-      if ((size_t)grid * parts > h->tlog_cnt_cap) {
-        (void)hipFree(h->d_tlog_cnt);
-        h->d_tlog_cnt = nullptr;
-        h->tlog_cnt_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_tlog_cnt, (size_t)grid * parts * 4));
-        h->tlog_cnt_cap = (size_t)grid * parts;
-      }
+      HIP_TRY(h, h->cnt.d_tlog.reserve(need));
+      HIP_TRY(h, h->cnt.d_tlog_cnt.reserve(logs));
     }
-    p.tlog = h->d_tlog;
-    p.tlog_cnt = h->d_tlog_cnt;
+    p.tlog = h->cnt.d_tlog;
+    p.tlog_cnt = h->cnt.d_tlog_cnt;
     p.tlog_cap = (uint32_t)cap;
     p.tlog_rshift = rshift;
     p.tlog_parts = parts;
@@ -757,16 +711,9 @@ int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs
   HIP_TRY(h, hipEventRecord(h->ring0[slot], h->stream));
   if (nb) {
     if (h->flags & kDbgTiming) {
-      const size_t n = (size_t)grid * (kWG / 64) * kTimingWords;
-      if (n > h->dbg_cap) {
-        (void)hipFree(h->d_dbg);
-        h->d_dbg = nullptr;
-        HIP_TRY(h, hipMalloc(&h->d_dbg, n * 8));
-        h->dbg_cap = n;
-      }
-      HIP_TRY(h, hipMemsetAsync(h->d_dbg, 0, n * 8, h->stream));
-      h->dbg_len = n;
-      p.dbg = reinterpret_cast<unsigned long long*>(h->d_dbg);
+      rc = ensure_dbg(h, (size_t)grid * (kWG / 64) * kTimingWords);
+      if (rc) return rc;
+      p.dbg = reinterpret_cast<unsigned long long*>(h->d_dbg.get());
       h->counters_fresh = false;
       HIP_TRY(h, launch_attribute(true, mode, grid, h->stream, p));
     } else {
@@ -779,8 +726,8 @@ int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs
       TlogParams r;
       r.tlog = p.tlog;
       r.tlog_cnt = p.tlog_cnt;
-      r.sum64 = h->d_sum64;
-      r.min64 = h->d_min64;
+      r.sum64 = h->cnt.d_sum64;
+      r.min64 = h->cnt.d_min64;
       r.pk64 = p.pk64;
       r.grid = grid;
       r.parts = p.tlog_parts;
@@ -791,7 +738,7 @@ int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs
       HIP_TRY(h, launch_tlog_reduce(p.tlog_parts, h->stream, r));
     } else if (p.pk64) {
       const uint32_t blocks = (uint32_t)std::min<uint64_t>(2048, (2ull * h->E + 255) / 256);
-      HIP_TRY(h, launch_unpack(blocks, h->stream, h->d_sum64, p.pk64, h->E, p.pk_shift));
+      HIP_TRY(h, launch_unpack(blocks, h->stream, h->cnt.d_sum64, p.pk64, h->E, p.pk_shift));
     }
   }
   if (!nb) {

@@ -68,27 +68,27 @@ static void build_big_lookup(const uint64_t* keys, uint32_t K, bool no_dir, BigL
 // chain[] (ids in DevEntry::id): node records, then the LDS Eytzinger tree
 // (<= kLdsNodes keys) or the fences + directory of the large-table path.
 // chain_dev: chain already on the device (the by-id array), else uploaded.
-int build_lookup(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
-                        const std::vector<DevEntry>& chain, DevEntry* chain_dev) {
-  h->K = nb_keys;
+int build_lookup(nmg_engine* h, LookupSet& l, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
+                 const std::vector<DevEntry>& chain, DevEntry* chain_dev) {
+  l.K = nb_keys;
   std::vector<DevEntry> nodes(nb_keys);
   for (uint32_t k = 0; k < nb_keys; k++) {
     nodes[k] = chain[entry_off[k]];
     nodes[k].first = entry_off[k];
     nodes[k].count = entry_off[k + 1] - entry_off[k];
   }
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_keys, keys, (size_t)nb_keys * 8));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_nodes, nodes.data(), (size_t)nb_keys * sizeof(DevEntry)));
-  if (chain_dev) h->d_chain = chain_dev;
-  else HIP_TRY(h, alloc_copy(h, (void**)&h->d_chain, chain.data(), chain.size() * sizeof(DevEntry)));
+  HIP_TRY(h, alloc_copy(h, l.keys, keys, nb_keys));
+  HIP_TRY(h, alloc_copy(h, l.nodes, nodes));
+  if (!chain_dev) HIP_TRY(h, alloc_copy(h, l.own_chain, chain));
+  l.chain = chain_dev ? chain_dev : l.own_chain.get();
   if (nb_keys <= kLdsNodes) {
     // Eytzinger (BFS) order for the LDS search: an in-order walk of the
     // complete tree of 2^L - 1 nodes hands out the keys in sorted order; the
     // slots after the last key are ~0 keys carrying a copy of the last node
     // (reached only for addr == UINT64_MAX, where the last key is the answer)
-    h->elevels = 0;
-    while (((1u << h->elevels) - 1) < nb_keys) h->elevels++;
-    const uint32_t n = 1u << h->elevels;
+    l.elevels = 0;
+    while (((1u << l.elevels) - 1) < nb_keys) l.elevels++;
+    const uint32_t n = 1u << l.elevels;
     std::vector<uint64_t> ef(n, ~0ull);
     std::vector<DevEntry> en(n);
     memset(en.data(), 0, n * sizeof(DevEntry));
@@ -111,19 +111,19 @@ int build_lookup(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off,
       r++;
       i = 2 * i + 1;
     }
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_efences, ef.data(), n * 8));
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_enodes, en.data(), n * sizeof(DevEntry)));
+    HIP_TRY(h, alloc_copy(h, l.efences, ef));
+    HIP_TRY(h, alloc_copy(h, l.enodes, en));
   }
-  h->nb_fences = h->fence_log2 = h->dir_log2 = 0;
+  l.nb_fences = l.fence_log2 = l.dir_log2 = 0;
   if (nb_keys > kLdsNodes) {
     BigLookup bl;
     build_big_lookup(keys, nb_keys, (h->flags & kDbgNoDir) != 0, bl);
-    h->nb_fences = bl.nb_fences;
-    h->fence_log2 = bl.fence_log2;
-    h->dir_log2 = bl.dir_log2;
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_ffences, bl.efences.data(), bl.efences.size() * 8));
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_fshift, bl.shift.data(), bl.shift.size()));
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_dir, bl.dir.data(), bl.dir.size() * sizeof(uint2)));
+    l.nb_fences = bl.nb_fences;
+    l.fence_log2 = bl.fence_log2;
+    l.dir_log2 = bl.dir_log2;
+    HIP_TRY(h, alloc_copy(h, l.ffences, bl.efences));
+    HIP_TRY(h, alloc_copy(h, l.fshift, bl.shift));
+    HIP_TRY(h, alloc_copy(h, l.dir, bl.dir));
   }
   return NMG_OK;
 }
@@ -197,7 +197,7 @@ void route_segments(const uint64_t* b, uint32_t P, RSeg* seg, uint32_t* nseg, st
 // per-object levels are outputs of the local pass too (local_kernel's extras).
 int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t K,
                             const std::vector<DevEntry>& dev, const uint32_t* ids) {
-  free_route_table(h);
+  h->rt = RouteTable();
   if (K <= kLdsNodes || !(h->flags & NMG_F_MATCH_SAMPLES)) return NMG_OK;
   if (ids) {  // the identity map is the offline case
     uint32_t e = 0;
@@ -389,25 +389,26 @@ int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_
     for (uint32_t e = parts[q].e0; d && e < parts[q].e0 + parts[q].ne; e++) d = dev[e].free == 0;
     if (d) dead[q >> 5] |= 1u << (q & 31);
   }
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pdead, dead.data(), dead.size() * 4));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_parts, parts.data(), parts.size() * sizeof(PartInfo)));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pbounds, pb.data(), pb.size() * 8));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pdir, rdir.data(), rdir.size() * 2));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_keys, pk.data(), pk.size() * 8));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_nodes, pn.data(), pn.size() * sizeof(uint4)));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_pnode, ppn.data(), ppn.size() * sizeof(uint4)));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_old, pold.data(), pold.size() * sizeof(uint4)));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_oinf, poinf.data(), poinf.size() * 4));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_info, pinf.data(), pinf.size() * sizeof(uint2)));
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_dir, pdir.data(), pdir.size() * sizeof(uint4)));
+  RouteTable& rt = h->rt;
+  HIP_TRY(h, alloc_copy(h, rt.d_pdead, dead));
+  HIP_TRY(h, alloc_copy(h, rt.d_parts, parts));
+  HIP_TRY(h, alloc_copy(h, rt.d_pbounds, pb));
+  HIP_TRY(h, alloc_copy(h, rt.d_pdir, rdir));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_keys, pk));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_nodes, pn));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_pnode, ppn));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_old, pold));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_oinf, poinf));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_info, pinf));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_dir, pdir));
   if (ids) {
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_ids, ids, (size_t)entry_off[K] * 4));
-    HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_lrel, lrel.data(), lrel.size() * 4));
-    if (!cmap.empty()) HIP_TRY(h, alloc_copy(h, (void**)&h->d_pe_cmap, cmap.data(), cmap.size() * 4));
+    HIP_TRY(h, alloc_copy(h, rt.d_pe_ids, ids, entry_off[K]));
+    HIP_TRY(h, alloc_copy(h, rt.d_pe_lrel, lrel));
+    if (!cmap.empty()) HIP_TRY(h, alloc_copy(h, rt.d_pe_cmap, cmap));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (pageable sources)
-  h->nparts = P;
-  h->route_ok = true;
+  rt.nparts = P;
+  rt.ok = true;
   return NMG_OK;
 }
 
@@ -415,7 +416,7 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
                                uint32_t nb_keys, const nmg_object* entries, uint32_t nb_entries) {
   if (h) h->epoch++;
   if (h) h->counters_fresh = false;
-  if (h) h->snap.meta_dirty = h->cprep.meta_dirty = true;
+  if (h) h->snap.lay.meta_dirty = h->cprep.lay.meta_dirty = true;
   Range range("nmg_set_objects");
   if (!h || (nb_keys && (!keys || !entry_off)) || (nb_entries && !entries))
     return NMG_ERR_INVALID;
@@ -424,9 +425,9 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
   if (nb_entries >= (1u << 31)) return fail(h, NMG_ERR_RANGE, "too many entries");
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  free_table(h);
-  free_counters(h);
-  h->K = nb_keys;
+  free_table(h);  // (released before the new ones are allocated: no second table's worth of HBM)
+  h->cnt = Counters();
+  h->lk.K = nb_keys;
   h->E = nb_entries;
 
   // page-histogram layout: dense [page][thread] block per entry within the
@@ -472,8 +473,8 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
       h->sparse_entries.push_back(e);
     }
   }
-  HIP_TRY(h, alloc_copy(h, (void**)&h->d_entries, dev.data(), (size_t)nb_entries * sizeof(DevEntry)));
-  rc = build_lookup(h, keys, entry_off, nb_keys, dev, h->d_entries);
+  HIP_TRY(h, alloc_copy(h, h->d_entries, dev));
+  rc = build_lookup(h, h->lk, keys, entry_off, nb_keys, dev, h->d_entries);
   if (rc) return rc;
   rc = build_partitions(h, keys, entry_off, nb_keys, dev, nullptr);
   if (rc) return rc;
@@ -484,23 +485,23 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
   if (h->flags & NMG_F_OBJECT_LEVELS) h->n_sum64 += (uint64_t)nb_entries * 2 * kLevelWords;
   h->n_min64 = 36 + (uint64_t)nb_entries + 1;
   h->n_max64 = 36;
-  HIP_TRY(h, hipMalloc(&h->d_sum64, h->n_sum64 * 8));
-  HIP_TRY(h, hipMalloc(&h->d_min64, h->n_min64 * 8));
-  HIP_TRY(h, hipMalloc(&h->d_max64, h->n_max64 * 8));
-  if (!h->d_found) HIP_TRY(h, hipMalloc(&h->d_found, 8));
+  HIP_TRY(h, h->cnt.d_sum64.alloc(h->n_sum64));
+  HIP_TRY(h, h->cnt.d_min64.alloc(h->n_min64));
+  HIP_TRY(h, h->cnt.d_max64.alloc(h->n_max64));
+  HIP_TRY(h, h->d_found.reserve(1));
   if (nb_entries > kObjSlots) {  // hashed object mode (see launch_attribution)
-    HIP_TRY(h, hipMalloc(&h->d_pk64, (size_t)nb_entries * 2 * 8));
-    HIP_TRY(h, hipMemset(h->d_pk64, 0, (size_t)nb_entries * 2 * 8));
+    HIP_TRY(h, h->cnt.d_pk64.alloc((size_t)nb_entries * 2));
+    HIP_TRY(h, hipMemset(h->cnt.d_pk64, 0, (size_t)nb_entries * 2 * 8));
   }
   // pad the dense arena to a multiple of 4 cells per thread so it is zeroed in 16 B units
   h->hist_cells = (h->hist_cells + 3) & ~uint64_t(3);
-  if (h->hist_cells) HIP_TRY(h, hipMalloc(&h->d_hist, h->hist_cells * h->T * 4));
+  if (h->hist_cells) HIP_TRY(h, h->cnt.d_hist.alloc(h->hist_cells * h->T));
   if (!h->sparse_entries.empty()) {
-    HIP_TRY(h, hipMalloc(&h->d_sparse_keys, h->sparse_cap * 8));
-    HIP_TRY(h, hipMalloc(&h->d_sparse_vals, h->sparse_cap * 4));
-    HIP_TRY(h, hipMalloc(&h->d_sparse_dirty, 2 * 4));
+    HIP_TRY(h, h->cnt.d_sparse_keys.alloc(h->sparse_cap));
+    HIP_TRY(h, h->cnt.d_sparse_vals.alloc(h->sparse_cap));
+    HIP_TRY(h, h->cnt.d_sparse_dirty.alloc(2));
     const uint32_t ones[2] = {1u, 1u};  // the first reset clears the fresh table
-    HIP_TRY(h, hipMemcpy(h->d_sparse_dirty, ones, 8, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->cnt.d_sparse_dirty, ones, 8, hipMemcpyHostToDevice));
   }
   h->have_table = true;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -605,57 +606,48 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
   const uint64_t n_sum = 2 * kGlobalSums + (uint64_t)newE * 4 +
                          ((h->flags & NMG_F_OBJECT_LEVELS) ? (uint64_t)newE * 2 * kLevelWords : 0);
   const uint64_t n_min = 36 + (uint64_t)newE + 1;
-  uint64_t *sum = nullptr, *mn = nullptr;
-  uint32_t* hist = nullptr;
-  unsigned long long* pk = nullptr;
-  DevEntry* ent = nullptr;
-  uint64_t* skeys = nullptr;
-  uint32_t *svals = nullptr, *sdirty = nullptr;
-  const bool new_sparse = nsparse0 == 0 && !h->sparse_entries.empty() && !h->d_sparse_keys;
+  DevBuf<uint64_t> sum, mn, skeys;
+  DevBuf<uint32_t> hist, svals, sdirty;
+  DevBuf<unsigned long long> pk;
+  DevBuf<DevEntry> ent;
+  const bool new_sparse = nsparse0 == 0 && !h->sparse_entries.empty() && !h->cnt.d_sparse_keys;
+  // (the new arrays are released on return, after the copies into them have drained)
   auto undo = [&](hipError_t e, const char* what) {
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(sum);
-    (void)hipFree(mn);
-    (void)hipFree(hist);
-    (void)hipFree(pk);
-    (void)hipFree(ent);
-    (void)hipFree(skeys);
-    (void)hipFree(svals);
-    (void)hipFree(sdirty);
     return fail_rb(NMG_ERR_HIP, std::string("nmg_update_objects: ") + what + ": " + hipGetErrorString(e));
   };
   hipError_t e;
-  if ((e = hipMalloc(&sum, n_sum * 8)) != hipSuccess) return undo(e, "counters");
-  if ((e = hipMalloc(&mn, n_min * 8)) != hipSuccess) return undo(e, "ordinals");
-  if (cells && cells * T != oldCells * T && (e = hipMalloc(&hist, cells * T * 4)) != hipSuccess)
+  if ((e = sum.alloc(n_sum)) != hipSuccess) return undo(e, "counters");
+  if ((e = mn.alloc(n_min)) != hipSuccess) return undo(e, "ordinals");
+  if (cells && cells * T != oldCells * T && (e = hist.alloc(cells * T)) != hipSuccess)
     return undo(e, "page histogram");
-  if (newE > kObjSlots && (e = hipMalloc(&pk, (size_t)newE * 2 * 8)) != hipSuccess) return undo(e, "packed counters");
-  if ((e = hipMalloc(&ent, (size_t)newE * sizeof(DevEntry))) != hipSuccess) return undo(e, "entries");
+  if (newE > kObjSlots && (e = pk.alloc((size_t)newE * 2)) != hipSuccess) return undo(e, "packed counters");
+  if ((e = ent.alloc(newE)) != hipSuccess) return undo(e, "entries");
   hipStream_t st = h->stream;
   if (new_sparse) {  // the first sparse entry: its table
-    if ((e = hipMalloc(&skeys, h->sparse_cap * 8)) != hipSuccess || (e = hipMalloc(&svals, h->sparse_cap * 4)) != hipSuccess ||
-        (e = hipMalloc(&sdirty, 2 * 4)) != hipSuccess || (e = hipMemsetAsync(skeys, 0xff, h->sparse_cap * 8, st)) != hipSuccess ||
+    if ((e = skeys.alloc(h->sparse_cap)) != hipSuccess || (e = svals.alloc(h->sparse_cap)) != hipSuccess ||
+        (e = sdirty.alloc(2)) != hipSuccess || (e = hipMemsetAsync(skeys, 0xff, h->sparse_cap * 8, st)) != hipSuccess ||
         (e = hipMemsetAsync(svals, 0, h->sparse_cap * 4, st)) != hipSuccess ||
         (e = hipMemsetAsync(sdirty, 0, 2 * 4, st)) != hipSuccess)
       return undo(e, "sparse page table");
   }
   if ((e = hipMemsetAsync(sum, 0, n_sum * 8, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(sum, h->d_sum64, 2 * kGlobalSums * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
-      (oldE && (e = hipMemcpy2DAsync(sum + 2 * kGlobalSums, (size_t)newE * 8, h->d_sum64 + 2 * kGlobalSums,
+      (e = hipMemcpyAsync(sum, h->cnt.d_sum64, 2 * kGlobalSums * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+      (oldE && (e = hipMemcpy2DAsync(sum + 2 * kGlobalSums, (size_t)newE * 8, h->cnt.d_sum64 + 2 * kGlobalSums,
                                      (size_t)oldE * 8, (size_t)oldE * 8, 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
       ((h->flags & NMG_F_OBJECT_LEVELS) && oldE &&
-       (e = hipMemcpyAsync(sum + 2 * kGlobalSums + (uint64_t)newE * 4, h->d_sum64 + 2 * kGlobalSums + (uint64_t)oldE * 4,
+       (e = hipMemcpyAsync(sum + 2 * kGlobalSums + (uint64_t)newE * 4, h->cnt.d_sum64 + 2 * kGlobalSums + (uint64_t)oldE * 4,
                            (size_t)oldE * 2 * kLevelWords * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
       (e = hipMemsetAsync(mn, 0xff, n_min * 8, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(mn, h->d_min64, (36 + (size_t)oldE) * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(mn + 36 + newE, h->d_min64 + 36 + oldE, 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(mn, h->cnt.d_min64, (36 + (size_t)oldE) * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(mn + 36 + newE, h->cnt.d_min64 + 36 + oldE, 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
       (pk && (e = hipMemsetAsync(pk, 0, (size_t)newE * 2 * 8, st)) != hipSuccess) ||
       (e = hipMemcpyAsync(ent, h->dev_entries.data(), (size_t)newE * sizeof(DevEntry), hipMemcpyHostToDevice, st)) !=
           hipSuccess)
     return undo(e, "re-layout");
   if (hist) {  // [thread][cell] rows with the new stride; moved entries' counts to their new range
     if ((e = hipMemsetAsync(hist, 0, cells * T * 4, st)) != hipSuccess ||
-        (oldCells && (e = hipMemcpy2DAsync(hist, cells * 4, h->d_hist, oldCells * 4, oldCells * 4, T,
+        (oldCells && (e = hipMemcpy2DAsync(hist, cells * 4, h->cnt.d_hist, oldCells * 4, oldCells * 4, T,
                                            hipMemcpyDeviceToDevice, st)) != hipSuccess))
       return undo(e, "page histogram re-layout");
     for (const Move& m : moves)
@@ -665,27 +657,21 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
         return undo(e, "page cells of a grown object");
   }
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return undo(e, "re-layout");
-  (void)hipFree(h->d_sum64);
-  (void)hipFree(h->d_min64);
-  (void)hipFree(h->d_pk64);
-  if (h->d_chain == h->d_entries) h->d_chain = ent;
-  (void)hipFree(h->d_entries);
-  h->d_sum64 = sum;
-  h->d_min64 = mn;
-  h->d_pk64 = pk;
-  h->d_entries = ent;
-  if (hist) {
-    (void)hipFree(h->d_hist);
-    h->d_hist = hist;
-  }
+  // commit: the old arrays are released as the new ones move in
+  if (!h->lk.own_chain) h->lk.chain = ent;  // (the table order is still the id order)
+  h->cnt.d_sum64 = std::move(sum);
+  h->cnt.d_min64 = std::move(mn);
+  h->cnt.d_pk64 = std::move(pk);
+  h->d_entries = std::move(ent);
+  if (hist) h->cnt.d_hist = std::move(hist);
   h->n_sum64 = n_sum;
   h->n_min64 = n_min;
   h->hist_cells = cells;
   h->E = newE;
   if (new_sparse) {
-    h->d_sparse_keys = skeys;
-    h->d_sparse_vals = svals;
-    h->d_sparse_dirty = sdirty;
+    h->cnt.d_sparse_keys = std::move(skeys);
+    h->cnt.d_sparse_vals = std::move(svals);
+    h->cnt.d_sparse_dirty = std::move(sdirty);
   }
   return NMG_OK;
 }
@@ -699,7 +685,7 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
                                   uint32_t nb_keys, const uint32_t* entry_ids, const nmg_object* objects) {
   if (h) h->epoch++;
   if (h) h->counters_fresh = false;  // (grown objects' page cells move)
-  if (h) h->snap.meta_dirty = h->cprep.meta_dirty = true;
+  if (h) h->snap.lay.meta_dirty = h->cprep.lay.meta_dirty = true;
   Range range("nmg_update_objects");
   if (!h || (nb_keys && (!keys || !entry_off || !entry_ids || !objects))) return NMG_ERR_INVALID;
   if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_update_objects before nmg_set_objects");
@@ -750,24 +736,17 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
     d.free = o.free_date;
     d.count = d.first = 0;
   }
-  free_route_table(h);  // (the partitions describe the previous table)
+  h->rt = RouteTable();  // (the partitions describe the previous table)
   // build the alarm's lookup beside the current one; keep the current one if that fails
-  const LookupSet prev = take_lookup(h);
-  rc = build_lookup(h, keys, entry_off, nb_keys, chain, nullptr);
+  LookupSet next;
+  rc = build_lookup(h, next, keys, entry_off, nb_keys, chain, nullptr);
   if (rc == NMG_OK && hipStreamSynchronize(h->stream) != hipSuccess)
     rc = fail(h, NMG_ERR_HIP, "nmg_update_objects: table upload failed");
   if (rc) {
-    (void)hipStreamSynchronize(h->stream);
-    free_lookup(h);
-    put_lookup(h, prev);
+    (void)hipStreamSynchronize(h->stream);  // (`next` is released on return, after its uploads)
     return rc;
   }
-  {
-    const LookupSet cur = take_lookup(h);
-    put_lookup(h, prev);
-    free_lookup(h);  // (keeps d_chain when it is the by-id entry array)
-    put_lookup(h, cur);
-  }
+  h->lk = std::move(next);
   // the report's view: every listed entry as this table lists it, and this
   // table's order when it lists every entry (ma_finalize walks the table it
   // has at exit, FOREACH_HASH, mem_analyzer.c:1381-1383)
@@ -793,7 +772,7 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
   // the same table (a half-applied update would leave them on the old one).
   if (build_partitions(h, keys, entry_off, nb_keys, chain, entry_ids) != NMG_OK) {
     (void)hipGetLastError();
-    free_route_table(h);
+    h->rt = RouteTable();
   }
   for (nmg_engine* w : h->workers) {  // multi-GPU: the table on every device
     rc = nmg_update_objects(w, keys, entry_off, nb_keys, entry_ids, objects);

@@ -161,3 +161,52 @@ def test_results_snapshot_survives_table_switch():
         assert np.array_equal(np.asarray(x), np.asarray(y)), name
     eng.synchronize()
     eng.close()
+
+
+def _round_outputs(eng, rp, levels):
+    """One round on `eng`: the table, the buffers through the pinned staging,
+    the analysis, every getter and a results snapshot (copied out of the
+    engine's pinned memory)."""
+    eng.clear_buffers()
+    eng.set_objects(rp.table)
+    eng.submit_replay(rp)
+    eng.analyze()
+    out = list(_sync_results(eng))
+    if levels:
+        out.append(eng.object_levels())
+    eng.results_begin()
+    out.extend(np.array(x) for x in eng.results_end())
+    return out, eng.route_count()
+
+
+@pytest.mark.parametrize("levels", [False, True], ids=["default", "object_levels"])
+def test_engine_reuse_across_growing_and_shrinking_sizes(levels):
+    """One engine through a small table, a large one (partition-first path)
+    and a small one again, with 4, 64 and 8 buffers: every device and pinned
+    buffer of the engine is grown once and then kept while the next round
+    needs less, the table and its counters are swapped twice, and the engine
+    is destroyed after all of it.  Every round's outputs equal those of a
+    fresh engine given only that round."""
+    from numamma_amd import _lib
+    from numamma_amd.engine import Engine
+
+    flags = _lib.NMG_F_DEFAULT | (_lib.NMG_F_OBJECT_LEVELS if levels else 0)
+    # (nb_intervals, buffer_records, buffers): 60 000 samples, half reads, over
+    # 2 threads -> four blocks of 15 000 records, cut into buffers
+    rounds = [(300, 15_000, 4), (3_000, 938, 64), (300, 7_500, 8)]
+    eng = Engine(nb_threads=2, flags=flags)
+    for i, (k, recs, nbuf) in enumerate(rounds):
+        rp = generate(SynthConfig(nb_samples=60_000, nb_intervals=k, nb_threads=2, read_frac=0.5, buffer_records=recs,
+                                  size_max=4 << 20, seed=31 + i))
+        assert len(rp.buffers) == nbuf
+        routed0 = eng.route_count()
+        got, routed = _round_outputs(eng, rp, levels)
+        assert (routed > routed0) == (k == 3_000), i  # (small tables: attribute_kernel)
+        fresh = Engine(nb_threads=2, flags=flags)
+        want, _ = _round_outputs(fresh, rp, levels)
+        fresh.close()
+        assert len(got) == len(want) == (17 if levels else 16)
+        assert want[7].shape[0] > 0 and want[2] > 0, i  # (page-cell rows, matched samples)
+        for j, (x, y) in enumerate(zip(got, want)):
+            assert np.array_equal(np.asarray(x), np.asarray(y)), (i, j)
+    eng.close()
