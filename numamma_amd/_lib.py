@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from .results import NB_BUCKETS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (NMG_LIB_PATH: another in-tree build of the same library, for A/B timing
 # of two kernel versions on one box; tools/ab_lib.sh.  Every export must still
@@ -67,7 +69,7 @@ class nmg_mem_counters(C.Structure):
         ("total_count", C.c_uint64),
         ("total_weight", C.c_uint64),
         ("na_miss_count", C.c_uint64),
-        ("b", nmg_count * 18),
+        ("b", nmg_count * NB_BUCKETS),
     ]
 
 

@@ -83,7 +83,7 @@ __device__ __forceinline__ uint32_t bucket_mask(uint32_t lvl) {
 __device__ __forceinline__ void level_count(const Params& p, uint64_t e, uint32_t access, uint32_t lvl, uint64_t w,
                                             unsigned long long n = 1ull) {
   unsigned long long* lv = reinterpret_cast<unsigned long long*>(
-      p.sum64 + 2 * kGlobalSums + uint64_t(p.nb_entries) * 4 + (e * 2 + access) * kLevelWords);
+      p.sum64 + kCwBase + uint64_t(p.nb_entries) * kCwRows + (e * 2 + access) * kLevelWords);
   if (lvl & LVL_NA) atomicAdd(lv, n);
   for (int g = 0; g < 9; g++) {
     if (!(lvl & level_mask(g))) continue;
@@ -96,7 +96,7 @@ __device__ __forceinline__ void level_count(const Params& p, uint64_t e, uint32_
 
 __device__ __forceinline__ void set_error(const Params& p, uint64_t seq, uint32_t off, uint32_t code) {
   uint64_t w = (seq << 40) | (uint64_t(off) << 8) | code;
-  atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + 36 + p.nb_entries),
+  atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + p.nb_entries),
             (unsigned long long)w);
 }
 
@@ -237,7 +237,7 @@ __device__ __forceinline__ void lane_acc_drain(LaneAcc& a, unsigned long long* s
 
 // update_counters(global_counters, sample) (mem_sampling.c:517-592) for one
 // SAMPLE of level field `lvl` and weight w: per-lane registers for the common
-// buckets, the workgroup's LDS words (sums [kGlobalSums], mins / maxs [18])
+// buckets, the workgroup's LDS words (sums [kGlobalSums], mins / maxs [kBuckets])
 // for the rest.
 __device__ __forceinline__ void global_count(LaneAcc& acc, unsigned long long* sums, unsigned long long* mins,
                                              unsigned long long* maxs, uint32_t lvl, uint64_t w) {

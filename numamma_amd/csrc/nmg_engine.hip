@@ -14,9 +14,9 @@ namespace nmg {
 uint32_t engine_nb_threads(nmg_engine* h) { return h->T; }
 uint32_t engine_nb_entries(nmg_engine* h) { return h->E; }
 uint32_t engine_flags(nmg_engine* h) { return h->flags; }
-const std::vector<uint64_t>& engine_hist_base(nmg_engine* h) { return h->hist_base; }
-const std::vector<uint64_t>& engine_npages(nmg_engine* h) { return h->npages; }
-const std::vector<uint32_t>& engine_sparse_entries(nmg_engine* h) { return h->sparse_entries; }
+const std::vector<uint64_t>& engine_hist_base(nmg_engine* h) { return h->tab.hist_base; }
+const std::vector<uint64_t>& engine_npages(nmg_engine* h) { return h->tab.npages; }
+const std::vector<uint32_t>& engine_sparse_entries(nmg_engine* h) { return h->tab.sparse_entries; }
 void engine_set_error(nmg_engine* h, const std::string& msg) { h->last_error = msg; }
 }  // namespace nmg
 
@@ -243,13 +243,13 @@ extern "C" int nmg_reset_counters(nmg_engine* h) {
   ResetParams r;
   memset(&r, 0, sizeof(r));
   r.sum64 = h->cnt.d_sum64;
-  r.n_sum64 = h->n_sum64;
+  r.n_sum64 = h->cnt.n_sum64;
   r.min64 = h->cnt.d_min64;
-  r.n_min64 = h->n_min64;
+  r.n_min64 = h->cnt.n_min64;
   r.max64 = h->cnt.d_max64;
-  r.n_max64 = h->n_max64;
+  r.n_max64 = h->cnt.n_max64;
   r.found = h->d_found;
-  const uint64_t hist_bytes = h->hist_cells * h->T * 4;
+  const uint64_t hist_bytes = h->tab.cells() * h->T * 4;
   if (hist_bytes & 15) HIP_TRY(h, hipMemsetAsync(h->cnt.d_hist, 0, hist_bytes, h->stream));  // (16 B multiple always)
   r.hist = reinterpret_cast<uint4*>(h->cnt.d_hist.get());
   r.n_hist16 = hist_bytes / 16;
@@ -358,7 +358,7 @@ extern "C" int nmg_synchronize(nmg_engine* h) {
   }
   if (!h->have_table) return NMG_OK;
   uint64_t w = ~0ull;
-  HIP_TRY(h, hipMemcpy(&w, h->cnt.d_min64 + 36 + h->E, 8, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(&w, h->cnt.d_min64 + error_index(h->E), 8, hipMemcpyDeviceToHost));
   return decode_error_word(h, w);
 }
 
@@ -442,14 +442,14 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   res.buf_samples = r.buf_samples.data();
   res.buf_found = r.buf_found.data();
   res.buf_bytes = r.buf_bytes.data();
-  res.buffer_size = h->buffer_size.data();
+  res.buffer_size = h->tab.buffer_size.data();
   res.first_ordinal = r.first.data();
   res.count_weight = r.count_weight.data();
   res.cells = rows.data();
   res.nb_cells = ncells;
   res.nb_threads = h->T;
   res.match_samples = (h->flags & NMG_F_MATCH_SAMPLES) ? 1 : 0;
-  res.objects = h->objects.data();
+  res.objects = h->tab.objects.data();
   // live online tables: entries walked in the order of the latest table that
   // listed them all (ids are creation order there); meta follows that order
   std::vector<uint64_t> w_size, w_first, w_cw;
@@ -467,10 +467,10 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
     for (uint32_t k = 0; k < E; k++) {
       const uint32_t id = h->order[k];
       pos[id] = k;
-      w_size[k] = h->buffer_size[id];
+      w_size[k] = h->tab.buffer_size[id];
       w_first[k] = r.first[id];
       for (int q = 0; q < 4; q++) w_cw[(size_t)k * 4 + q] = r.count_weight[(size_t)id * 4 + q];
-      w_obj[k] = h->objects[id];
+      w_obj[k] = h->tab.objects[id];
     }
     // page rows (entry, thread, page, count), grouped by walk position
     std::vector<uint32_t> idx((size_t)ncells);
@@ -515,7 +515,7 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
     }
     for (const BufDesc& d : h->descs)
       dump.buffers.push_back({base + d.offset, d.len, d.thread_rank, d.access, smatch.data() + d.offset / 8});
-    dump.entry_addr = h->entry_addr.data();
+    dump.entry_addr = h->tab.entry_addr.data();
     dump.levels = r.levels.data();
   }
   std::string err;

@@ -159,9 +159,72 @@ struct RoutePool {
   DevBuf<unsigned long long> d_ovfx;
 };
 
-// the counter arrays of one table (nmg_set_objects releases them with it)
+// The host's entry table: per entry id, the object as the latest table lists
+// it and the page cells it counts into.  The arrays are contiguous (the report
+// and the uploads read their data()).
+struct EntryTable {
+  std::vector<uint64_t> hist_base;  // first dense cell, kHistSparse if sparse / none
+  std::vector<uint64_t> npages;     // buffer_size / kPageSize + 1 of the cells it has
+  std::vector<uint64_t> buffer_size, entry_addr;
+  std::vector<nmg_object> objects;    // the report's objects
+  std::vector<DevEntry> dev_entries;  // host copy of d_entries (cells and id; nmg_set_objects' table also its objects)
+  std::vector<uint32_t> sparse_entries;  // sparse idx -> entry
+  CellCursor cur;  // cur.cells: dense cells per thread (padded between calls)
+
+  uint64_t cells() const { return cur.cells; }
+  // E entries; new ones are objects not described yet: one page, no cells
+  void resize(uint32_t E) {
+    const size_t E0 = dev_entries.size();
+    hist_base.resize(E, kHistSparse);
+    npages.resize(E, 1);
+    buffer_size.resize(E, 0);
+    entry_addr.resize(E, 0);
+    objects.resize(E, nmg_object{0, 0, 0, 0});
+    dev_entries.resize(E, DevEntry{0, 0, 0, 0, kHistSparse, ~0u, 0, 0, 0, 0});
+    for (size_t e = E0; e < E; e++) dev_entries[e].id = (uint32_t)e;
+  }
+  // what resize and place added since the table had E entries and cursor c, dropped again
+  void truncate(uint32_t E, const CellCursor& c) {
+    resize(E);
+    sparse_entries.resize(c.nsparse);
+    cur = c;
+  }
+  // entry id as object o describes it (the report's view)
+  void describe(uint32_t id, const nmg_object& o) {
+    objects[id] = o;
+    buffer_size[id] = o.buffer_size;
+    entry_addr[id] = o.buffer_addr;
+  }
+  // the device record of entry id (its cells) as object o describes it
+  DevEntry dev_entry(uint32_t id, const nmg_object& o) const {
+    DevEntry d = dev_entries[id];
+    d.addr = o.buffer_addr;
+    d.end = o.buffer_addr + o.buffer_size;
+    d.alloc = o.alloc_date;
+    d.free = o.free_date;
+    return d;
+  }
+  // page cells for np pages of entry id (CellCursor::place); the entry is unchanged unless placed
+  Placement place(uint32_t id, uint64_t np, bool must_be_dense) {
+    DevEntry& d = dev_entries[id];
+    uint64_t base = kHistSparse;
+    const Placement how = cur.place(np, must_be_dense, &base, &d.sidx);
+    if (how == kPlaceDense) d.hist = hist_base[id] = base;
+    if (how == kPlaceSparse) sparse_entries.push_back(id);
+    return how;
+  }
+};
+
+// the counter arrays of one table (nmg_set_objects releases them with it),
+// n_* their word counts (nmg_internal.h's layout for the table's entries)
 struct Counters {
   DevBuf<uint64_t> d_sum64, d_min64, d_max64;
+  uint64_t n_sum64 = 0, n_min64 = 0, n_max64 = 0;
+  void set_sizes(uint64_t E, bool levels) {
+    n_sum64 = sum64_words(E, levels);
+    n_min64 = min64_words(E);
+    n_max64 = max64_words();
+  }
   DevBuf<uint32_t> d_hist;
   DevBuf<uint64_t> d_sparse_keys;
   DevBuf<uint32_t> d_sparse_vals;
@@ -249,19 +312,14 @@ struct nmg_engine {
   uint32_t E = 0;
   LookupSet lk;
   DevBuf<DevEntry> d_entries;  // by entry id (the nmg_set_objects table)
-  std::vector<uint64_t> hist_base, npages, buffer_size, entry_addr;
-  std::vector<DevEntry> dev_entries;  // host copy of d_entries (nmg_update_objects builds from it)
-  std::vector<nmg_object> objects;  // each entry as the latest table lists it (the report's objects)
+  EntryTable tab;  // E entries
   std::vector<uint32_t> order;      // report walk order (position -> id) when it is not the id order:
                                     // the latest table that listed every entry (nmg_update_objects)
-  std::vector<uint32_t> sparse_entries;
-  uint64_t hist_cells = 0;
   uint64_t hist_budget = 4ull << 30;
   uint64_t sparse_cap = 1u << 20;
 
   // counters
   Counters cnt;
-  uint64_t n_sum64 = 0, n_min64 = 0, n_max64 = 0;
   DevBuf<unsigned long long> d_found;  // matched SAMPLEs since the last reset (Params::found)
   DevBuf<uint64_t> d_scratch;          // [2] small device results (nmg_hist_pack / unpack) + range counts
   DevBuf<uint32_t> d_smatch;           // NMG_F_SAMPLE_MATCHES: per 8 B of the arena span

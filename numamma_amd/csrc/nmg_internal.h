@@ -9,23 +9,91 @@
 
 namespace nmg {
 
-// Layout of the flat merge arrays (see nmg_export_array):
-//   sum64: [2 access][39] global sums   (total_count, total_weight, na_miss_count,
-//                                         18 x (count, sum_weight))
-//          [2 access][2][E]              per-entry count, weight (SoA: a flush in
-//                                         entry order coalesces its atomics)
-//          [E][2 access][37]             per-entry levels (na, 18 x (count, sum)), optional
-//   min64: [2][18] global bucket min_weight, [E] first-match ordinal, [1] error word
-//   max64: [2][18] global bucket max_weight
-constexpr uint32_t kGlobalSums = 39;
-constexpr uint32_t kLevelWords = 37;
+// Layout of the flat merge arrays (see nmg_export_array), in u64 words.  This
+// is the one description of it: device code, host code and the Python mirror
+// (numamma_amd/results.py) take every offset and size from the names below.
+//   sum64: [2 access][kGlobalSums]     global sums: total_count, total_weight,
+//                                       na_miss_count, kBuckets x (count, sum_weight)
+//          [2 access][2][E]             per-entry count, weight (SoA: a flush in
+//                                       entry order coalesces its atomics)
+//          [E][2 access][kLevelWords]   per-entry levels: na_miss_count,
+//                                       kBuckets x (count, sum_weight); NMG_F_OBJECT_LEVELS only
+//   min64: [2 access][kBuckets]         global bucket min_weight
+//          [E]                          first-match ordinal
+//          [1]                          error word
+//   max64: [2 access][kBuckets]         global bucket max_weight
+constexpr uint32_t kBuckets = NMG_NB_BUCKETS;
+constexpr uint32_t kGlobalSums = 3 + 2 * kBuckets;  // per access
+constexpr uint32_t kLevelWords = 1 + 2 * kBuckets;  // per entry and access
+constexpr uint32_t kGlobalMinMax = 2 * kBuckets;    // min64's and max64's global words
+constexpr uint32_t kCwBase = 2 * kGlobalSums;       // sum64: the count/weight rows start here
+constexpr uint32_t kCwRows = 4;                     // [2 access][2] rows of E words
+constexpr uint32_t kFirstBase = kGlobalMinMax;      // min64: the first ordinals start here
+// a mem_counters' words are its sums plus a min and a max per bucket
+static_assert(sizeof(nmg_count) == 4 * 8 && sizeof(nmg_mem_counters) == (kGlobalSums + 2 * kBuckets) * 8,
+              "the merge arrays hold struct nmg_mem_counters word for word");
 constexpr uint64_t kHistSparse = ~0ull;
 constexpr uint32_t kPageSize = 4096;  // src/mem_analyzer.c:471
 
 constexpr uint64_t gsum_index(uint32_t access, uint32_t i) { return access * kGlobalSums + i; }
 constexpr uint64_t objcw_index(uint64_t e, uint32_t access, uint32_t w, uint64_t nb_entries) {
-  return 2 * kGlobalSums + (uint64_t(access) * 2 + w) * nb_entries + e;
+  return kCwBase + (uint64_t(access) * 2 + w) * nb_entries + e;
 }
+constexpr uint64_t levels_base(uint64_t nb_entries) { return kCwBase + kCwRows * nb_entries; }
+constexpr uint64_t levels_index(uint64_t e, uint32_t access, uint64_t nb_entries) {
+  return levels_base(nb_entries) + (e * 2 + access) * kLevelWords;
+}
+constexpr uint64_t gminmax_index(uint32_t access, uint32_t bucket) { return access * kBuckets + bucket; }
+constexpr uint64_t first_index(uint64_t e) { return kFirstBase + e; }
+constexpr uint64_t error_index(uint64_t nb_entries) { return kFirstBase + nb_entries; }
+constexpr uint64_t sum64_words(uint64_t nb_entries, bool levels) {
+  return levels_base(nb_entries) + (levels ? nb_entries * 2 * kLevelWords : 0);
+}
+constexpr uint64_t min64_words(uint64_t nb_entries) { return error_index(nb_entries) + 1; }
+constexpr uint64_t max64_words() { return kGlobalMinMax; }
+// both access types' struct mem_counters from the arrays' global words
+inline void global_counters(const uint64_t* sum, const uint64_t* mn, const uint64_t* mx, nmg_mem_counters out[2]) {
+  for (uint32_t a = 0; a < 2; a++) {
+    nmg_mem_counters& c = out[a];
+    const uint64_t* s = sum + gsum_index(a, 0);
+    c.total_count = s[0];
+    c.total_weight = s[1];
+    c.na_miss_count = s[2];
+    for (uint32_t k = 0; k < kBuckets; k++)
+      c.b[k] = nmg_count{s[3 + 2 * k], mn[gminmax_index(a, k)], mx[gminmax_index(a, k)], s[4 + 2 * k]};
+  }
+}
+
+// Page cells of the table's entries.  An entry of np pages gets a dense block
+// of np cells per thread (histogram index = thread * cells + base + page)
+// while the block, the budget and the 32-bit cell index allow it; otherwise
+// it becomes a sparse entry, its cells hashed on demand.
+constexpr uint64_t kMaxEntryCells = 1ull << 24;   // np * threads of one dense entry
+constexpr uint64_t kMaxCellIndex = 0xffffffffull;  // dense cells per thread stay below it
+constexpr uint32_t kMaxSparse = 1u << 22;         // sparse entries (sparse_key's index field)
+enum Placement { kPlaceDense, kPlaceSparse, kPlaceOverBudget, kPlaceSparseFull };
+struct CellCursor {
+  uint64_t threads = 1, budget_cells = 0;  // budget: dense cells over all threads
+  uint64_t cells = 0;                      // dense cells per thread handed out so far
+  uint32_t nsparse = 0;                    // sparse entries so far
+  // Place an entry of np pages: kPlaceDense with *base its first cell,
+  // kPlaceSparse with *sidx its sparse index, or why neither (the cursor is
+  // then unchanged).  must_be_dense: an entry that already has dense cells
+  // (its counts move with it) never turns sparse.
+  Placement place(uint64_t np, bool must_be_dense, uint64_t* base, uint32_t* sidx) {
+    if (np * threads <= kMaxEntryCells && (cells + np) * threads <= budget_cells && cells + np < kMaxCellIndex) {
+      *base = cells;
+      cells += np;
+      return kPlaceDense;
+    }
+    if (must_be_dense) return kPlaceOverBudget;
+    if (nsparse >= kMaxSparse) return kPlaceSparseFull;
+    *sidx = nsparse++;
+    return kPlaceSparse;
+  }
+  // the dense arena is zeroed in 16 B units: a multiple of 4 cells per thread
+  uint64_t padded_cells() const { return (cells + 3) & ~uint64_t(3); }
+};
 
 // Error word: min over ((seq << 40) | (byte offset << 8) | code) so the first
 // failing record in analysis order wins, as the reference's abort() would.
@@ -45,8 +113,8 @@ struct HostResults {
   std::vector<uint32_t> buf_samples, buf_found;
   std::vector<uint64_t> buf_bytes;
   std::vector<uint64_t> first;        // [E]
-  std::vector<uint64_t> count_weight; // [E][2][2]
-  std::vector<uint64_t> levels;       // [E][2][37] (empty unless NMG_F_OBJECT_LEVELS)
+  std::vector<uint64_t> count_weight; // [E][2][2] (kCwRows words per entry)
+  std::vector<uint64_t> levels;       // [E][2][kLevelWords] (empty unless NMG_F_OBJECT_LEVELS)
 };
 
 // ---- engine accessors used by the report writer (implemented in nmg_engine.hip)

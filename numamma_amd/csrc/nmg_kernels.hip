@@ -117,9 +117,9 @@ __device__ __forceinline__ uint32_t lower_key(const Params& p, const uint64_t* s
 // being analysed.  One stream at a time per workgroup, so (entry) and
 // (entry, page) are the keys of the aggregation tables.
 struct WgCounters {
-  unsigned long long sums[kGlobalSums];  // total_count, total_weight, na, 18 x (count, sum)
-  unsigned long long mins[18];
-  unsigned long long maxs[18];
+  unsigned long long sums[kGlobalSums];  // total_count, total_weight, na, kBuckets x (count, sum)
+  unsigned long long mins[kBuckets];
+  unsigned long long maxs[kBuckets];
   alignas(16) unsigned int okey[kObjSlots];  // entry id, 8 per bucket (hashed modes)
   unsigned long long ofirst[kObjSlots];  // smallest (seq << 32 | offset): first match
   unsigned long long owt[kObjSlots];     // count << kPackShift | weight sum (weights < kLaneMaxWeight)
@@ -329,14 +329,14 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
     // table full: logged for tlog_reduce_kernel
   } else if (pk) {  // table full: one packed global add
     atomicAdd(p.pk64 + uint64_t(access) * p.nb_entries + e, (1ull << p.pk_shift) | w);
-    unsigned long long* fp = reinterpret_cast<unsigned long long*>(p.min64 + 36 + e);
+    unsigned long long* fp = reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + e);
     atomicMin(fp, ord);
   } else {  // table full (or a weight >= 2^23 in dense mode): straight to global
     atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, access, 0, p.nb_entries)), 1ull);
     if (w)
       atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, access, 1, p.nb_entries)),
                 (unsigned long long)w);
-    unsigned long long* fp = reinterpret_cast<unsigned long long*>(p.min64 + 36 + e);
+    unsigned long long* fp = reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + e);
     atomicMin(fp, ord);
   }
   sub_stamp<TIMING>(st, 2);
@@ -380,14 +380,14 @@ __device__ __forceinline__ void flush_objects(Params& p, WgCounters& wc, int tid
       // logged
     } else if (write && !(MODE & kModeDenseObj) && p.pk64) {
       atomicAdd(p.pk64 + uint64_t(a) * p.nb_entries + e, (cnt << p.pk_shift) | wt);
-      atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + 36 + e), wc.ofirst[i]);
+      atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + e), wc.ofirst[i]);
     } else if (write) {
       atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, a, 0, p.nb_entries)),
                 (unsigned long long)cnt);
       if (wt)
         atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, a, 1, p.nb_entries)),
                   (unsigned long long)wt);
-      unsigned long long* fp = reinterpret_cast<unsigned long long*>(p.min64 + 36 + e);
+      unsigned long long* fp = reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + e);
       atomicMin(fp, wc.ofirst[i]);  // no read first: a returning load would stall the flush
     }
     wc.okey[i] = kEmpty32;
@@ -430,10 +430,10 @@ __device__ __forceinline__ void flush_sums(Params& p, WgCounters& wc, int tid, u
     if (write && wc.sums[tid])
       atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + gsum_index(a, tid)), wc.sums[tid]);
   }
-  if (tid < 18) {
+  if (tid < (int)kBuckets) {
     if (write && wc.sums[3 + 2 * tid]) {
-      atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + a * 18 + tid), wc.mins[tid]);
-      atomicMax(reinterpret_cast<unsigned long long*>(p.max64 + a * 18 + tid), wc.maxs[tid]);
+      atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + a * kBuckets + tid), wc.mins[tid]);
+      atomicMax(reinterpret_cast<unsigned long long*>(p.max64 + a * kBuckets + tid), wc.maxs[tid]);
     }
   }
   // (cleared after a barrier: sums[3 + 2 * tid] is read by other threads above)
@@ -441,7 +441,7 @@ __device__ __forceinline__ void flush_sums(Params& p, WgCounters& wc, int tid, u
 
 __device__ __forceinline__ void clear_sums(WgCounters& wc, int tid) {
   if (tid < (int)kGlobalSums) wc.sums[tid] = 0;
-  if (tid < 18) {
+  if (tid < (int)kBuckets) {
     wc.mins[tid] = ~0ull;  // INIT_COUNTER: min = UINT64_MAX (mem_analyzer.c:415-420)
     wc.maxs[tid] = 0;
   }
@@ -908,7 +908,7 @@ __global__ __launch_bounds__(1024, 1) void tlog_reduce_kernel(TlogParams r) {
           gw[u][a] = r.sum64[objcw_index(e, a, 1, r.nb_entries)];
           pv[u][a] = r.pk64 ? r.pk64[uint64_t(a) * r.nb_entries + e] : 0;
         }
-        gm[u] = r.min64[36 + e];
+        gm[u] = r.min64[kFirstBase + e];
       }
 #pragma unroll
       for (int u = 0; u < kU; u++) {
@@ -927,7 +927,7 @@ __global__ __launch_bounds__(1024, 1) void tlog_reduce_kernel(TlogParams r) {
           if (c) r.sum64[objcw_index(e, a, 0, r.nb_entries)] = gc[u][a] + c;
           if (w) r.sum64[objcw_index(e, a, 1, r.nb_entries)] = gw[u][a] + w;
         }
-        if (s_ord[j] < gm[u]) r.min64[36 + e] = s_ord[j];
+        if (s_ord[j] < gm[u]) r.min64[kFirstBase + e] = s_ord[j];
       }
     }
     __syncthreads();

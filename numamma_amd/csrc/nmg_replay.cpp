@@ -229,7 +229,7 @@ int write_raw(nmg_engine* h, const Replay& r, const char* path) {
     fwrite(&c.total_count, 8, 1, f);
     fwrite(&c.total_weight, 8, 1, f);
     fwrite(&c.na_miss_count, 8, 1, f);
-    for (int k = 0; k < 18; k++) fwrite(&c.b[k], 8, 4, f);
+    for (uint32_t k = 0; k < nmg::kBuckets; k++) fwrite(&c.b[k], 8, 4, f);
   }
   fwrite(&res.nb_samples_total, 8, 1, f);
   fwrite(&res.nb_found_total, 8, 1, f);
@@ -237,19 +237,19 @@ int write_raw(nmg_engine* h, const Replay& r, const char* path) {
   fwrite(res.buf_found.data(), 4, res.buf_found.size(), f);
   const bool lv = !res.levels.empty();
   for (uint32_t e = 0; e < E; e++) {
-    uint64_t rec[1 + 2 * 39] = {0};
+    uint64_t rec[1 + 2 * nmg::kGlobalSums] = {0};  // first, [2 access] x (count, weight, level words)
     rec[0] = res.first[e];
     for (int a = 0; a < 2; a++) {
-      uint64_t* q = rec + 1 + 39 * a;
-      q[0] = res.count_weight[(uint64_t)e * 4 + a * 2 + 0];
-      q[1] = res.count_weight[(uint64_t)e * 4 + a * 2 + 1];
+      uint64_t* q = rec + 1 + nmg::kGlobalSums * a;
+      q[0] = res.count_weight[(uint64_t)e * nmg::kCwRows + a * 2 + 0];
+      q[1] = res.count_weight[(uint64_t)e * nmg::kCwRows + a * 2 + 1];
       if (lv) {
         const uint64_t* l = res.levels.data() + ((uint64_t)e * 2 + a) * nmg::kLevelWords;
         q[2] = l[0];
-        for (int k = 0; k < 36; k++) q[3 + k] = l[1 + k];
+        for (uint32_t k = 1; k < nmg::kLevelWords; k++) q[2 + k] = l[k];
       }
     }
-    fwrite(rec, 8, 1 + 2 * 39, f);
+    fwrite(rec, 8, 1 + 2 * nmg::kGlobalSums, f);
   }
   uint64_t n = (uint64_t)ncells;
   fwrite(&n, 8, 1, f);

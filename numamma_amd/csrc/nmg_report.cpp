@@ -635,7 +635,7 @@ int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const n
           cc[a].total_count += cw[0];
           cc[a].total_weight += cw[1];
           cc[a].na_miss_count += lv[0];
-          for (int k = 0; k < 18; k++) {
+          for (uint32_t k = 0; k < kBuckets; k++) {
             cc[a].b[k].count += lv[1 + 2 * k];
             cc[a].b[k].sum_weight += lv[2 + 2 * k];
           }

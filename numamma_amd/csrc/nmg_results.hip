@@ -18,32 +18,20 @@ int engine_download(nmg_engine* h, HostResults& r, bool entries, bool buffer_fou
   if (rc) return rc;
   // (entries == false: the global counters and per-buffer counts only, not
   // the per-entry arrays -- 40 MB at 1M entries)
-  const uint64_t ns = entries ? h->n_sum64 : 2 * kGlobalSums, nm = entries ? h->n_min64 : 36;
-  std::vector<uint64_t> sum(ns), mn(nm), mx(h->n_max64);
+  const uint64_t ns = entries ? h->cnt.n_sum64 : kCwBase, nm = entries ? h->cnt.n_min64 : kFirstBase;
+  std::vector<uint64_t> sum(ns), mn(nm), mx(h->cnt.n_max64);
   HIP_TRY(h, hipMemcpy(sum.data(), h->cnt.d_sum64, ns * 8, hipMemcpyDeviceToHost));
   HIP_TRY(h, hipMemcpy(mn.data(), h->cnt.d_min64, nm * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(h, hipMemcpy(mx.data(), h->cnt.d_max64, h->n_max64 * 8, hipMemcpyDeviceToHost));
-  for (int a = 0; a < 2; a++) {
-    nmg_mem_counters& c = r.global[a];
-    const uint64_t* s = sum.data() + gsum_index(a, 0);
-    c.total_count = s[0];
-    c.total_weight = s[1];
-    c.na_miss_count = s[2];
-    for (int k = 0; k < 18; k++) {
-      c.b[k].count = s[3 + 2 * k];
-      c.b[k].sum_weight = s[4 + 2 * k];
-      c.b[k].min_weight = mn[a * 18 + k];
-      c.b[k].max_weight = mx[a * 18 + k];
-    }
-  }
+  HIP_TRY(h, hipMemcpy(mx.data(), h->cnt.d_max64, h->cnt.n_max64 * 8, hipMemcpyDeviceToHost));
+  global_counters(sum.data(), mn.data(), mx.data(), r.global);
   const uint64_t E = entries ? h->E : 0;
-  r.first.assign(mn.begin() + 36, mn.begin() + 36 + E);
-  r.count_weight.resize(4 * E);  // SoA [2][2][E] -> [E][2][2]
+  r.first.assign(mn.begin() + first_index(0), mn.begin() + first_index(E));
+  r.count_weight.resize(kCwRows * E);  // SoA [2][2][E] -> [E][2][2]
   for (uint64_t e = 0; e < E; e++)
     for (uint32_t a = 0; a < 2; a++)
-      for (uint32_t w = 0; w < 2; w++) r.count_weight[e * 4 + a * 2 + w] = sum[objcw_index(e, a, w, E)];
+      for (uint32_t w = 0; w < 2; w++) r.count_weight[e * kCwRows + a * 2 + w] = sum[objcw_index(e, a, w, E)];
   if ((h->flags & NMG_F_OBJECT_LEVELS) && entries)
-    r.levels.assign(sum.begin() + 2 * kGlobalSums + 4 * E, sum.end());
+    r.levels.assign(sum.begin() + levels_base(E), sum.end());
   else
     r.levels.clear();
   // mem_sampling_finalize accumulates the per-buffer int counters (:334-335);
@@ -86,8 +74,8 @@ int engine_download(nmg_engine* h, HostResults& r, bool entries, bool buffer_fou
 int engine_download_hist(nmg_engine* h, std::vector<uint32_t>& cells) {
   int rc = nmg_synchronize(h);
   if (rc) return rc;
-  cells.resize(h->hist_cells * h->T);
-  if (h->hist_cells) HIP_TRY(h, hipMemcpy(cells.data(), h->cnt.d_hist, cells.size() * 4, hipMemcpyDeviceToHost));
+  cells.resize(h->tab.cells() * h->T);
+  if (h->tab.cells()) HIP_TRY(h, hipMemcpy(cells.data(), h->cnt.d_hist, cells.size() * 4, hipMemcpyDeviceToHost));
   return NMG_OK;
 }
 }  // namespace nmg
@@ -123,13 +111,13 @@ extern "C" int nmg_get_object_counters(nmg_engine* h, uint64_t* first_ordinal, u
   int rc = nmg_synchronize(h);
   if (rc) return rc;
   if (first_ordinal && h->E)
-    HIP_TRY(h, hipMemcpy(first_ordinal, h->cnt.d_min64 + 36, (size_t)h->E * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(first_ordinal, h->cnt.d_min64 + kFirstBase, (size_t)h->E * 8, hipMemcpyDeviceToHost));
   if (count_weight && h->E) {  // the SoA rows laid out per entry on the device, then one copy
     static_assert(objcw_index(1, 0, 0, 8) - objcw_index(0, 0, 0, 8) == 1 && objcw_index(0, 0, 1, 8) - objcw_index(0, 0, 0, 8) == 8 &&
                       objcw_index(0, 1, 0, 8) - objcw_index(0, 0, 0, 8) == 16,
                   "objcw_aos_kernel reads rows access * 2 + w");
     HIP_TRY(h, h->cnt.d_objcw.reserve((size_t)h->E * 4));
-    HIP_TRY(h, launch_objcw_aos(h->stream, h->cnt.d_sum64 + 2 * kGlobalSums, h->E, h->cnt.d_objcw));
+    HIP_TRY(h, launch_objcw_aos(h->stream, h->cnt.d_sum64 + kCwBase, h->E, h->cnt.d_objcw));
     HIP_TRY(h, hipMemcpyAsync(count_weight, h->cnt.d_objcw, (size_t)h->E * 32, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
@@ -142,7 +130,7 @@ extern "C" int nmg_get_object_levels(nmg_engine* h, uint64_t* levels) {
   int rc = nmg_synchronize(h);
   if (rc) return rc;
   if (h->E)
-    HIP_TRY(h, hipMemcpy(levels, h->cnt.d_sum64 + 2 * kGlobalSums + (uint64_t)h->E * 4,
+    HIP_TRY(h, hipMemcpy(levels, h->cnt.d_sum64 + levels_base(h->E),
                          (size_t)h->E * 2 * kLevelWords * 8, hipMemcpyDeviceToHost));
   return NMG_OK;
 }
@@ -174,13 +162,13 @@ int CellLayout::ensure(nmg_engine* h, uint64_t newE, uint64_t new_nsent) {
 // entries as the current table has them (sparse idx -> entry, ~0: no longer
 // sparse -- an online update gave it dense cells)
 static void cell_layout_host(nmg_engine* h, std::vector<uint32_t>& np, std::vector<uint32_t>& sent_entry) {
-  const uint64_t E = h->E, nsent = h->sparse_entries.size();
+  const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   np.resize(E);
-  for (uint64_t e = 0; e < E; e++) np[e] = h->hist_base[e] == kHistSparse ? 0u : (uint32_t)h->npages[e];
+  for (uint64_t e = 0; e < E; e++) np[e] = h->tab.hist_base[e] == kHistSparse ? 0u : (uint32_t)h->tab.npages[e];
   sent_entry.resize(nsent);
   for (uint64_t s = 0; s < nsent; s++) {
-    const uint32_t e = h->sparse_entries[s];
-    sent_entry[s] = h->hist_base[e] == kHistSparse ? e : ~0u;
+    const uint32_t e = h->tab.sparse_entries[s];
+    sent_entry[s] = h->tab.hist_base[e] == kHistSparse ? e : ~0u;
   }
 }
 
@@ -236,7 +224,7 @@ int cells_prepare(nmg_engine* h) {
   int rc = nmg_synchronize(h);
   if (rc) return rc;
   lap("sync");
-  const uint64_t E = h->E, nsent = h->sparse_entries.size();
+  const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   auto& P = h->cprep;
   CellLayout& C = P.lay;
   rc = C.ensure(h, E, nsent);
@@ -245,10 +233,10 @@ int cells_prepare(nmg_engine* h) {
     std::vector<uint32_t> np;
     cell_layout_host(h, np, P.sent_entry);
     if (E) {
-      HIP_TRY(h, hipMemcpy(C.d_base, h->hist_base.data(), E * 8, hipMemcpyHostToDevice));
+      HIP_TRY(h, hipMemcpy(C.d_base, h->tab.hist_base.data(), E * 8, hipMemcpyHostToDevice));
       HIP_TRY(h, hipMemcpy(C.d_np, np.data(), E * 4, hipMemcpyHostToDevice));
     }
-    if (nsent) HIP_TRY(h, hipMemcpy(C.d_sent, h->sparse_entries.data(), nsent * 4, hipMemcpyHostToDevice));
+    if (nsent) HIP_TRY(h, hipMemcpy(C.d_sent, h->tab.sparse_entries.data(), nsent * 4, hipMemcpyHostToDevice));
     C.meta_dirty = false;
   }
   lap("meta");
@@ -264,14 +252,14 @@ int cells_prepare(nmg_engine* h) {
     P.sparse_kv[2 * i + 1] = v[i];
   }
   lap("sparse");
-  const bool dense = h->hist_cells && E;
+  const bool dense = h->tab.cells() && E;
   uint64_t n = 0;
   std::vector<uint64_t>& soff = P.soff;
   soff.assign(nsent, 0);
   if (E) {
     hipStream_t st = h->stream;
     if (dense)
-      HIP_TRY(h, launch_cells_count(st, h->cnt.d_hist, h->hist_cells, h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
+      HIP_TRY(h, launch_cells_count(st, h->cnt.d_hist, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
     else
       HIP_TRY(h, hipMemsetAsync(C.d_cnt, 0, E * 4, st));
     if (!k.empty())
@@ -288,7 +276,7 @@ int cells_prepare(nmg_engine* h) {
     lap("count");
     if (dense && n) {
       HIP_TRY(h, P.d_rows.reserve(n));
-      HIP_TRY(h, launch_cells_emit(st, h->cnt.d_hist, h->hist_cells, h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off, P.d_rows));
+      HIP_TRY(h, launch_cells_emit(st, h->cnt.d_hist, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off, P.d_rows));
       HIP_TRY(h, hipStreamSynchronize(st));
     }
     lap("emit");
@@ -301,7 +289,7 @@ int cells_prepare(nmg_engine* h) {
 
 // the prepared rows into rows[cprep.n * 4]: dense rows D2H, sparse rows placed
 int cells_fill(nmg_engine* h, uint32_t* rows) {
-  const bool dense = h->hist_cells && h->E;
+  const bool dense = h->tab.cells() && h->E;
   const auto t0 = std::chrono::steady_clock::now();
   const auto& P = h->cprep;
   if (dense && P.n) HIP_TRY(h, hipMemcpy(rows, P.d_rows, (size_t)P.n * 16, hipMemcpyDeviceToHost));
@@ -338,20 +326,20 @@ extern "C" int nmg_get_page_cells(nmg_engine* h, uint32_t* rows, int64_t n) {
 extern "C" uint64_t nmg_array_size(nmg_engine* h, int which) {
   if (!h || !h->have_table) return 0;
   switch (which) {
-    case NMG_ARR_SUM64: return h->n_sum64;
-    case NMG_ARR_MIN64: return h->n_min64;
-    case NMG_ARR_MAX64: return h->n_max64;
-    case NMG_ARR_HIST32: return h->hist_cells * h->T;
+    case NMG_ARR_SUM64: return h->cnt.n_sum64;
+    case NMG_ARR_MIN64: return h->cnt.n_min64;
+    case NMG_ARR_MAX64: return h->cnt.n_max64;
+    case NMG_ARR_HIST32: return h->tab.cells() * h->T;
     default: return 0;
   }
 }
 
 void* array_ptr(nmg_engine* h, int which, size_t* bytes) {
   switch (which) {
-    case NMG_ARR_SUM64: *bytes = h->n_sum64 * 8; return h->cnt.d_sum64;
-    case NMG_ARR_MIN64: *bytes = h->n_min64 * 8; return h->cnt.d_min64;
-    case NMG_ARR_MAX64: *bytes = h->n_max64 * 8; return h->cnt.d_max64;
-    case NMG_ARR_HIST32: *bytes = h->hist_cells * h->T * 4; return h->cnt.d_hist;
+    case NMG_ARR_SUM64: *bytes = h->cnt.n_sum64 * 8; return h->cnt.d_sum64;
+    case NMG_ARR_MIN64: *bytes = h->cnt.n_min64 * 8; return h->cnt.d_min64;
+    case NMG_ARR_MAX64: *bytes = h->cnt.n_max64 * 8; return h->cnt.d_max64;
+    case NMG_ARR_HIST32: *bytes = h->tab.cells() * h->T * 4; return h->cnt.d_hist;
     default: *bytes = 0; return nullptr;
   }
 }
@@ -393,7 +381,7 @@ extern "C" int nmg_hist_pack(nmg_engine* h, uint32_t threshold, void* d_u8, void
                              uint64_t* n_ovf) {
   Range range("nmg_hist_pack");
   if (!h || !h->have_table || !n_ovf || threshold > 255) return NMG_ERR_INVALID;
-  const uint64_t cells = h->hist_cells * h->T;
+  const uint64_t cells = h->tab.cells() * h->T;
   *n_ovf = 0;
   if (!cells) return NMG_OK;
   if (!d_u8 || (ovf_cap && !d_ovf)) return NMG_ERR_INVALID;
@@ -415,7 +403,7 @@ extern "C" int nmg_hist_unpack(nmg_engine* h, const void* d_u8, const void* d_ov
   if (h) h->counters_fresh = false;
   Range range("nmg_hist_unpack");
   if (!h || !h->have_table || (n_ovf && !d_ovf)) return NMG_ERR_INVALID;
-  const uint64_t cells = h->hist_cells * h->T;
+  const uint64_t cells = h->tab.cells() * h->T;
   if (!cells) return NMG_OK;
   if (!d_u8) return NMG_ERR_INVALID;
   int rc = scratch_u64(h);
@@ -591,30 +579,30 @@ namespace nmg {
 // the buffer list outgrows them
 static int snap_alloc(nmg_engine* h) {
   auto& S = h->snap;
-  const uint64_t E = h->E, nb = h->descs.size(), nsent = h->sparse_entries.size();
-  const uint64_t rows = h->hist_cells * h->T + (h->cnt.d_sparse_keys ? h->sparse_cap : 0);
+  const uint64_t E = h->E, nb = h->descs.size(), nsent = h->tab.sparse_entries.size();
+  const uint64_t rows = h->tab.cells() * h->T + (h->cnt.d_sparse_keys ? h->sparse_cap : 0);
   if (!S.stream) {
     HIP_TRY(h, hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
     HIP_TRY(h, hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
     HIP_TRY(h, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
   }
   if (E != S.lay.E || !S.d_objcw) {
-    HIP_TRY(h, S.d_min.alloc(36 + E + 1));
+    HIP_TRY(h, S.d_min.alloc(min64_words(E)));
     HIP_TRY(h, S.d_objcw.alloc((E + 1) * 4));
   }
   const int rc = S.lay.ensure(h, E, nsent);
   if (rc) return rc;
-  HIP_TRY(h, S.d_sum.reserve(2 * kGlobalSums));
-  HIP_TRY(h, S.d_max.reserve(36));
+  HIP_TRY(h, S.d_sum.reserve(kCwBase));
+  HIP_TRY(h, S.d_max.reserve(max64_words()));
   HIP_TRY(h, S.d_found.reserve(1));
   HIP_TRY(h, S.d_bufcnt.reserve(2 * nb + 1));
   HIP_TRY(h, S.d_rows.reserve(rows + 1));
   if (h->cnt.d_sparse_keys) HIP_TRY(h, S.d_ck.reserve(2 * h->sparse_cap + 1));
   // pinned host copies (the rows grow on demand in nmg_results_end)
-  HIP_TRY(h, S.h_sum.reserve(2 * kGlobalSums));
-  HIP_TRY(h, S.h_max.reserve(36));
+  HIP_TRY(h, S.h_sum.reserve(kCwBase));
+  HIP_TRY(h, S.h_max.reserve(max64_words()));
   HIP_TRY(h, S.h_small.reserve(4));
-  HIP_TRY(h, S.h_min.reserve(36 + E + 1));
+  HIP_TRY(h, S.h_min.reserve(min64_words(E)));
   HIP_TRY(h, S.h_objcw.reserve((E + 1) * 4));
   HIP_TRY(h, S.h_bufcnt.reserve(2 * nb + 1));
   HIP_TRY(h, S.h_soff.reserve(nsent + 1));
@@ -640,7 +628,7 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
   if (rc) return rc;
   rc = snap_alloc(h);
   if (rc) return rc;
-  const uint64_t E = h->E, nb = h->descs.size(), nsent = h->sparse_entries.size();
+  const uint64_t E = h->E, nb = h->descs.size(), nsent = h->tab.sparse_entries.size();
   hipStream_t st = h->stream;
   CellLayout& L = S.lay;
   if (L.meta_dirty) {  // (the table's cell layout: uploaded once per table, through the
@@ -649,29 +637,29 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
     // the sparse rows with these, whatever table the engine holds by then
     std::vector<uint32_t> np;
     cell_layout_host(h, np, S.sent_entry);
-    rc = stage_h2d(h, L.d_base, h->hist_base.data(), E * 8);
+    rc = stage_h2d(h, L.d_base, h->tab.hist_base.data(), E * 8);
     if (!rc) rc = stage_h2d(h, L.d_np, np.data(), E * 4);
-    if (!rc) rc = stage_h2d(h, L.d_sent, h->sparse_entries.data(), nsent * 4);
+    if (!rc) rc = stage_h2d(h, L.d_sent, h->tab.sparse_entries.data(), nsent * 4);
     if (rc) return rc;
     L.meta_dirty = false;
   }
   // the device snapshot, behind the enqueued analyses
-  HIP_TRY(h, hipMemcpyAsync(S.d_sum, h->cnt.d_sum64, 2 * kGlobalSums * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(h, hipMemcpyAsync(S.d_min, h->cnt.d_min64, (36 + E) * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(h, hipMemcpyAsync(S.d_max, h->cnt.d_max64, 36 * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(h, hipMemcpyAsync(S.d_sum, h->cnt.d_sum64, kCwBase * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(h, hipMemcpyAsync(S.d_min, h->cnt.d_min64, first_index(E) * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(h, hipMemcpyAsync(S.d_max, h->cnt.d_max64, max64_words() * 8, hipMemcpyDeviceToDevice, st));
   if (nb) {
     HIP_TRY(h, hipMemcpyAsync(S.d_bufcnt, h->d_bufcnt, nb * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(S.d_bufcnt + nb, h->d_bufcnt + h->bufcnt_stride, nb * 4, hipMemcpyDeviceToDevice, st));
   }
   if (h->d_found) HIP_TRY(h, hipMemcpyAsync(S.d_found, h->d_found, 8, hipMemcpyDeviceToDevice, st));
   else HIP_TRY(h, hipMemsetAsync(S.d_found, 0, 8, st));
-  if (E) HIP_TRY(h, launch_objcw_aos(st, h->cnt.d_sum64 + 2 * kGlobalSums, E, S.d_objcw));
+  if (E) HIP_TRY(h, launch_objcw_aos(st, h->cnt.d_sum64 + kCwBase, E, S.d_objcw));
   // page-cell rows: per-entry counts (dense, then the sparse table's), their
   // exclusive scan, the dense rows; the sparse ones are placed by the host
   unsigned long long* nsp = S.d_ck ? reinterpret_cast<unsigned long long*>(S.d_ck + 2 * h->sparse_cap) : nullptr;
   if (E) {
-    if (h->hist_cells)
-      HIP_TRY(h, launch_cells_count(st, h->cnt.d_hist, h->hist_cells, h->T, L.d_base, L.d_np, (uint32_t)E, L.d_cnt));
+    if (h->tab.cells())
+      HIP_TRY(h, launch_cells_count(st, h->cnt.d_hist, h->tab.cells(), h->T, L.d_base, L.d_np, (uint32_t)E, L.d_cnt));
     else
       HIP_TRY(h, hipMemsetAsync(L.d_cnt, 0, E * 4, st));
     if (nsp) {
@@ -681,8 +669,8 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
                                            L.d_cnt));
     }
     HIP_TRY(h, launch_scan_u32(st, L.d_cnt, E, L.d_off, L.d_part));
-    if (h->hist_cells)
-      HIP_TRY(h, launch_cells_emit(st, h->cnt.d_hist, h->hist_cells, h->T, L.d_base, L.d_np, (uint32_t)E, L.d_off,
+    if (h->tab.cells())
+      HIP_TRY(h, launch_cells_emit(st, h->cnt.d_hist, h->tab.cells(), h->T, L.d_base, L.d_np, (uint32_t)E, L.d_off,
                                    S.d_rows));
     HIP_TRY(h, launch_gather_off(st, L.d_off, L.d_sent, (uint32_t)nsent, L.d_soff));
   } else {
@@ -692,9 +680,9 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
   // the copy to pinned host memory, on the snapshot's own stream
   hipStream_t cs = S.stream;
   HIP_TRY(h, hipStreamWaitEvent(cs, S.ready, 0));
-  HIP_TRY(h, hipMemcpyAsync(S.h_sum, S.d_sum, 2 * kGlobalSums * 8, hipMemcpyDeviceToHost, cs));
-  HIP_TRY(h, hipMemcpyAsync(S.h_min, S.d_min, (36 + E) * 8, hipMemcpyDeviceToHost, cs));
-  HIP_TRY(h, hipMemcpyAsync(S.h_max, S.d_max, 36 * 8, hipMemcpyDeviceToHost, cs));
+  HIP_TRY(h, hipMemcpyAsync(S.h_sum, S.d_sum, kCwBase * 8, hipMemcpyDeviceToHost, cs));
+  HIP_TRY(h, hipMemcpyAsync(S.h_min, S.d_min, first_index(E) * 8, hipMemcpyDeviceToHost, cs));
+  HIP_TRY(h, hipMemcpyAsync(S.h_max, S.d_max, max64_words() * 8, hipMemcpyDeviceToHost, cs));
   if (nb) HIP_TRY(h, hipMemcpyAsync(S.h_bufcnt, S.d_bufcnt, 2 * nb * 4, hipMemcpyDeviceToHost, cs));
   HIP_TRY(h, hipMemcpyAsync(S.h_small, S.d_found, 8, hipMemcpyDeviceToHost, cs));
   HIP_TRY(h, hipMemcpyAsync(S.h_small + 1, L.d_off + E, 8, hipMemcpyDeviceToHost, cs));
@@ -733,19 +721,7 @@ extern "C" int nmg_results_end(nmg_engine* h, nmg_results_view* out) {
     place_sparse_rows(kv.data(), nspc, S.sent_entry, S.h_soff, S.h_rows);
   }
   memset(out, 0, sizeof(*out));
-  for (int a = 0; a < 2; a++) {  // (as engine_download)
-    nmg_mem_counters& c = out->global[a];
-    const uint64_t* s = S.h_sum + gsum_index(a, 0);
-    c.total_count = s[0];
-    c.total_weight = s[1];
-    c.na_miss_count = s[2];
-    for (int k = 0; k < 18; k++) {
-      c.b[k].count = s[3 + 2 * k];
-      c.b[k].sum_weight = s[4 + 2 * k];
-      c.b[k].min_weight = S.h_min[a * 18 + k];
-      c.b[k].max_weight = S.h_max[a * 18 + k];
-    }
-  }
+  global_counters(S.h_sum, S.h_min, S.h_max, out->global);
   uint64_t ns = 0;
   for (uint64_t b = 0; b < nb; b++) ns += (uint64_t)(int64_t)(int32_t)S.h_bufcnt[b];
   out->nb_samples = ns;
@@ -754,7 +730,7 @@ extern "C" int nmg_results_end(nmg_engine* h, nmg_results_view* out) {
   out->nb_entries = (uint32_t)E;
   out->buffer_samples = S.h_bufcnt;
   out->buffer_found = S.h_bufcnt + nb;
-  out->first_ordinal = S.h_min + 36;
+  out->first_ordinal = S.h_min + kFirstBase;
   out->count_weight = S.h_objcw;
   out->nb_cells = (int64_t)nrows;
   out->cells = S.h_rows;

@@ -136,7 +136,7 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
   atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, acc, 0, p.nb_entries)), 1ull);
   if (w) atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + objcw_index(e, acc, 1, p.nb_entries)),
                    (unsigned long long)w);
-  atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + 36 + e), (unsigned long long)((seq << 32) | off));
+  atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + e), (unsigned long long)((seq << 32) | off));
   if (!(p.flags & NMG_F_PAGE_HIST)) return;
   const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
   if (m.hist != kHistSparse) {
@@ -200,7 +200,7 @@ __device__ __forceinline__ void racc_clear(RouteAcc& a) {
 // the record moves it.
 template <uint32_t ACC>
 __device__ __forceinline__ void route_count(RouteAcc& a, unsigned long long (*sums)[kGlobalSums],
-                                            unsigned long long (*mins)[18], unsigned long long (*maxs)[18],
+                                            unsigned long long (*mins)[kBuckets], unsigned long long (*maxs)[kBuckets],
                                             bool valid, uint32_t lvl, uint64_t w) {
   const uint32_t cls = rt_class(lvl);
   const bool big = w >= (1u << 16);
@@ -545,7 +545,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
   __shared__ uint4 s_desc[kDescLds];
   __shared__ uint32_t s_wlist[kWaves][64];  // slow path: the wave window's SAMPLE offsets
   __shared__ uint32_t s_taken, s_bnext;
-  __shared__ unsigned long long s_gsums[2][kGlobalSums], s_gmins[2][18], s_gmaxs[2][18];
+  __shared__ unsigned long long s_gsums[2][kGlobalSums], s_gmins[2][kBuckets], s_gmaxs[2][kBuckets];
   __shared__ SegL s_seg[kRouteSegs];
   __shared__ uint64_t s_segst[kRouteSegs];
   // the line stage: per partition a line of four compact records, its line
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
     s_bnext = r0;
   }
   if (tid < (int)kGlobalSums) s_gsums[0][tid] = s_gsums[1][tid] = 0;
-  if (tid < 18) {
+  if (tid < (int)kBuckets) {
     s_gmins[0][tid] = s_gmins[1][tid] = ~0ull;  // INIT_COUNTER (mem_analyzer.c:415-420)
     s_gmaxs[0][tid] = s_gmaxs[1][tid] = 0;
   }
@@ -967,9 +967,9 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
   for (uint32_t a = 0; a < 2; a++) {  // the global mem_counters of both access types
     if (tid < (int)kGlobalSums && s_gsums[a][tid])
       atomicAdd(reinterpret_cast<unsigned long long*>(p.sum64 + gsum_index(a, tid)), s_gsums[a][tid]);
-    if (tid < 18 && s_gsums[a][3 + 2 * tid]) {
-      atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + a * 18 + tid), s_gmins[a][tid]);
-      atomicMax(reinterpret_cast<unsigned long long*>(p.max64 + a * 18 + tid), s_gmaxs[a][tid]);
+    if (tid < (int)kBuckets && s_gsums[a][3 + 2 * tid]) {
+      atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + a * kBuckets + tid), s_gmins[a][tid]);
+      atomicMax(reinterpret_cast<unsigned long long*>(p.max64 + a * kBuckets + tid), s_gmaxs[a][tid]);
     }
   }
   // the open and next chunks' fill (claims end below 96: the 96th advanced
@@ -1768,7 +1768,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       if (floc != ~0ull) {
         s_first[i] = ~0ull;
         const uint64_t fo = ((lp.seq0 + (floc >> lp.xl.obits)) << 32) | ((floc & ((1ull << lp.xl.obits) - 1)) << 3);
-        uint64_t* pf = p.min64 + 36 + e;
+        uint64_t* pf = p.min64 + kFirstBase + e;
         if (clean) *pf = fo;
         else if (excl) *pf = min(l2_load(pf), fo);
         else atomicMin(reinterpret_cast<unsigned long long*>(pf), (unsigned long long)fo);

@@ -629,7 +629,7 @@ Params base_params(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, co
   p.efences = h->lk.efences;
   p.enodes = h->lk.enodes;
   p.sparse_mask = (uint32_t)(h->sparse_cap - 1);
-  p.hist_cells = h->hist_cells;
+  p.hist_cells = h->tab.cells();
   p.sum64 = h->cnt.d_sum64;
   p.min64 = h->cnt.d_min64;
   p.max64 = h->cnt.d_max64;
@@ -669,7 +669,7 @@ int launch_attribution(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs
   Params p = base_params(h, data, sdescs, ranges);
   // dense LDS tables when the table is small enough (DESIGN.md "Kernels");
   // large tables: their own kernel instances (fences + directory + node records)
-  const int mode = (h->E <= kObjSlots ? kModeDenseObj : 0) | (h->hist_cells <= kDensePageCells ? kModeDensePage : 0) |
+  const int mode = (h->E <= kObjSlots ? kModeDenseObj : 0) | (h->tab.cells() <= kDensePageCells ? kModeDensePage : 0) |
                    (p.lds_nodes ? 0 : kModeLarge);
   if (!(mode & kModeDenseObj) && h->cnt.d_pk64 && !(h->flags & kDbgNoPack)) {
     // < 2^cbits packed samples in this launch (only SAMPLE records of at

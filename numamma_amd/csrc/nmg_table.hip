@@ -204,7 +204,7 @@ int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_
     while (e < entry_off[K] && ids[e] == e) e++;
     if (e == entry_off[K]) ids = nullptr;
   }
-  if (ids && h->hist_cells >= (1ull << 31)) return NMG_OK;  // (cell indices of an online table: 32-bit)
+  if (ids && h->tab.cells() >= (1ull << 31)) return NMG_OK;  // (cell indices of an online table: 32-bit)
   const uint64_t T = h->T;
   std::vector<PartInfo> parts;
   // an online table: the partition's dense cells packed in LDS in table
@@ -234,7 +234,7 @@ int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_
       uint64_t ncb = cb, nce = ce, ncc = cc;
       for (uint32_t e = ea; e < eb; e++)
         if (dev[e].hist != kHistSparse) {
-          const uint64_t np = h->npages[dev[e].id];
+          const uint64_t np = h->tab.npages[dev[e].id];
           ncb = std::min<uint64_t>(ncb, dev[e].hist);
           nce = std::max<uint64_t>(nce, dev[e].hist + np);
           ncc += np;
@@ -258,7 +258,7 @@ int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_
       uint32_t off = 0;
       for (uint32_t e = pi.e0; e < pi.e0 + pi.ne; e++)
         if (dev[e].hist != kHistSparse) {
-          const uint32_t np = (uint32_t)h->npages[dev[e].id];
+          const uint32_t np = (uint32_t)h->tab.npages[dev[e].id];
           lrel[e] = off;
           for (uint32_t g = 0; g < np; g++) cmap.push_back((uint32_t)(dev[e].hist + g));
           off += np;
@@ -432,71 +432,38 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
 
   // page-histogram layout: dense [page][thread] block per entry within the
   // budget, otherwise sparse hashed cells (e.g. the 412 GB [stack] range)
-  const uint64_t T = h->T;
-  const uint64_t max_cells_per_entry = 1ull << 24;
-  h->hist_base.assign(nb_entries, kHistSparse);
-  h->npages.resize(nb_entries);
-  h->buffer_size.resize(nb_entries);
-  h->entry_addr.resize(nb_entries);
-  h->objects.assign(entries, entries + nb_entries);
+  EntryTable& tab = h->tab;
+  tab = EntryTable();
+  tab.cur.threads = h->T;
+  tab.cur.budget_cells = h->hist_budget / 4;
+  tab.resize(nb_entries);
   h->order.clear();
-  h->sparse_entries.clear();
-  h->hist_cells = 0;
-  std::vector<DevEntry> dev(nb_entries);
   const bool want_hist = (h->flags & NMG_F_PAGE_HIST) && (h->flags & NMG_F_MATCH_SAMPLES);
-  const uint64_t budget_cells = h->hist_budget / 4;
   for (uint32_t e = 0; e < nb_entries; e++) {
     const nmg_object& o = entries[e];
-    DevEntry& d = dev[e];
-    memset(&d, 0, sizeof(d));
-    d.addr = o.buffer_addr;
-    d.end = o.buffer_addr + o.buffer_size;
-    d.alloc = o.alloc_date;
-    d.free = o.free_date;
-    uint64_t np = o.buffer_size / kPageSize + 1;
-    h->npages[e] = np;
-    h->buffer_size[e] = o.buffer_size;
-    h->entry_addr[e] = o.buffer_addr;
-    d.hist = kHistSparse;
-    d.sidx = ~0u;
-    d.id = e;
-    if (!want_hist) continue;
-    // dense cells: histogram index = thread * hist_cells + hist_base(entry) + page
-    if (np * T <= max_cells_per_entry && (h->hist_cells + np) * T <= budget_cells &&
-        h->hist_cells + np < 0xffffffffull) {
-      d.hist = h->hist_cells;
-      h->hist_base[e] = h->hist_cells;
-      h->hist_cells += np;
-    } else {
-      if (h->sparse_entries.size() >= (1u << 22)) return fail(h, NMG_ERR_CAPACITY, "too many sparse entries");
-      d.sidx = (uint32_t)h->sparse_entries.size();
-      h->sparse_entries.push_back(e);
-    }
+    tab.describe(e, o);
+    tab.npages[e] = o.buffer_size / kPageSize + 1;
+    if (want_hist && tab.place(e, tab.npages[e], false) == kPlaceSparseFull)
+      return fail(h, NMG_ERR_CAPACITY, "too many sparse entries");
+    tab.dev_entries[e] = tab.dev_entry(e, o);
   }
-  HIP_TRY(h, alloc_copy(h, h->d_entries, dev));
-  rc = build_lookup(h, h->lk, keys, entry_off, nb_keys, dev, h->d_entries);
+  tab.cur.cells = tab.cur.padded_cells();
+  HIP_TRY(h, alloc_copy(h, h->d_entries, tab.dev_entries));
+  rc = build_lookup(h, h->lk, keys, entry_off, nb_keys, tab.dev_entries, h->d_entries);
   if (rc) return rc;
-  rc = build_partitions(h, keys, entry_off, nb_keys, dev, nullptr);
+  rc = build_partitions(h, keys, entry_off, nb_keys, tab.dev_entries, nullptr);
   if (rc) return rc;
-  h->dev_entries = std::move(dev);
-
-
-  h->n_sum64 = 2 * kGlobalSums + (uint64_t)nb_entries * 4;
-  if (h->flags & NMG_F_OBJECT_LEVELS) h->n_sum64 += (uint64_t)nb_entries * 2 * kLevelWords;
-  h->n_min64 = 36 + (uint64_t)nb_entries + 1;
-  h->n_max64 = 36;
-  HIP_TRY(h, h->cnt.d_sum64.alloc(h->n_sum64));
-  HIP_TRY(h, h->cnt.d_min64.alloc(h->n_min64));
-  HIP_TRY(h, h->cnt.d_max64.alloc(h->n_max64));
+  h->cnt.set_sizes(nb_entries, h->flags & NMG_F_OBJECT_LEVELS);
+  HIP_TRY(h, h->cnt.d_sum64.alloc(h->cnt.n_sum64));
+  HIP_TRY(h, h->cnt.d_min64.alloc(h->cnt.n_min64));
+  HIP_TRY(h, h->cnt.d_max64.alloc(h->cnt.n_max64));
   HIP_TRY(h, h->d_found.reserve(1));
   if (nb_entries > kObjSlots) {  // hashed object mode (see launch_attribution)
     HIP_TRY(h, h->cnt.d_pk64.alloc((size_t)nb_entries * 2));
     HIP_TRY(h, hipMemset(h->cnt.d_pk64, 0, (size_t)nb_entries * 2 * 8));
   }
-  // pad the dense arena to a multiple of 4 cells per thread so it is zeroed in 16 B units
-  h->hist_cells = (h->hist_cells + 3) & ~uint64_t(3);
-  if (h->hist_cells) HIP_TRY(h, h->cnt.d_hist.alloc(h->hist_cells * h->T));
-  if (!h->sparse_entries.empty()) {
+  if (h->tab.cells()) HIP_TRY(h, h->cnt.d_hist.alloc(h->tab.cells() * h->T));
+  if (!h->tab.sparse_entries.empty()) {
     HIP_TRY(h, h->cnt.d_sparse_keys.alloc(h->sparse_cap));
     HIP_TRY(h, h->cnt.d_sparse_vals.alloc(h->sparse_cap));
     HIP_TRY(h, h->cnt.d_sparse_dirty.alloc(2));
@@ -526,91 +493,50 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
   const uint32_t oldE = h->E;
   const uint64_t T = h->T;
   const bool want_hist = (h->flags & NMG_F_PAGE_HIST) && (h->flags & NMG_F_MATCH_SAMPLES);
-  const uint64_t max_cells_per_entry = 1ull << 24, budget_cells = h->hist_budget / 4;
-  const uint64_t oldCells = h->hist_cells;
-  uint64_t cells = oldCells;
-  struct Move {
-    uint64_t from, to, np;
-  };
-  std::vector<Move> moves;
-  const size_t nsparse0 = h->sparse_entries.size();
-  // Host state is changed in place below; every error return first undoes
-  // it (the sizes before the call, and the old fields of the entries that
-  // moved), so that a failed update keeps the engine as it was.
+  const bool levels = h->flags & NMG_F_OBJECT_LEVELS;
+  EntryTable& tab = h->tab;
+  const CellCursor cur0 = tab.cur;
+  const uint64_t oldCells = cur0.cells;
+  // The table is changed in place below, the cells and pages of every old
+  // entry that grows journalled first; every error return undoes it (the new
+  // entries dropped, the journal put back), so that a failed update keeps the
+  // engine as it was.
   struct Old {
     uint32_t id;
     uint64_t hist, np;
-    DevEntry d;
   };
   std::vector<Old> changed;
-  auto rollback = [&]() {
-    for (auto it = changed.rbegin(); it != changed.rend(); ++it) {
-      h->hist_base[it->id] = it->hist;
-      h->npages[it->id] = it->np;
-      h->dev_entries[it->id] = it->d;
-    }
-    h->hist_base.resize(oldE);
-    h->npages.resize(oldE);
-    h->buffer_size.resize(oldE);
-    h->entry_addr.resize(oldE);
-    h->objects.resize(oldE);
-    h->dev_entries.resize(oldE);
-    h->sparse_entries.resize(nsparse0);
-  };
   auto fail_rb = [&](int code, const std::string& msg) {
-    rollback();
+    for (auto it = changed.rbegin(); it != changed.rend(); ++it) {
+      tab.dev_entries[it->id].hist = tab.hist_base[it->id] = it->hist;
+      tab.npages[it->id] = it->np;
+    }
+    tab.truncate(oldE, cur0);
     return fail(h, code, msg);
   };
-  h->hist_base.resize(newE, kHistSparse);
-  h->npages.resize(newE, 1);
-  h->buffer_size.resize(newE, 0);
-  h->entry_addr.resize(newE, 0);
-  h->objects.resize(newE, nmg_object{0, 0, 0, 0});
-  h->dev_entries.resize(newE);
-  for (uint32_t e = oldE; e < newE; e++) {
-    DevEntry& d = h->dev_entries[e];
-    memset(&d, 0, sizeof(d));
-    d.hist = kHistSparse;
-    d.sidx = ~0u;
-    d.id = e;
-  }
+  tab.resize(newE);
   for (uint32_t j = 0; j < n; j++) {
     const uint32_t id = ids[j];
     const uint64_t np = objs[j].buffer_size / kPageSize + 1;
-    DevEntry& d = h->dev_entries[id];
     if (id >= oldE) {
-      h->npages[id] = np;
-      if (!want_hist) continue;
-      if (np * T <= max_cells_per_entry && (cells + np) * T <= budget_cells && cells + np < 0xffffffffull) {
-        d.hist = h->hist_base[id] = cells;
-        cells += np;
-      } else {
-        if (h->sparse_entries.size() >= (1u << 22)) return fail_rb(NMG_ERR_CAPACITY, "too many sparse entries");
-        d.sidx = (uint32_t)h->sparse_entries.size();
-        h->sparse_entries.push_back(id);
-      }
-    } else if (np > h->npages[id]) {
-      changed.push_back({id, h->hist_base[id], h->npages[id], d});
-      if (want_hist && h->hist_base[id] != kHistSparse) {
-        if (np * T > max_cells_per_entry || (cells + np) * T > budget_cells || cells + np >= 0xffffffffull)
-          return fail_rb(NMG_ERR_CAPACITY, "an object outgrew its page cells past the histogram budget");
-        moves.push_back({h->hist_base[id], cells, h->npages[id]});
-        d.hist = h->hist_base[id] = cells;
-        cells += np;
-      }
-      h->npages[id] = np;
+      tab.npages[id] = np;
+      if (want_hist && tab.place(id, np, false) == kPlaceSparseFull)
+        return fail_rb(NMG_ERR_CAPACITY, "too many sparse entries");
+    } else if (np > tab.npages[id]) {
+      changed.push_back({id, tab.hist_base[id], tab.npages[id]});
+      if (want_hist && tab.hist_base[id] != kHistSparse && tab.place(id, np, true) != kPlaceDense)
+        return fail_rb(NMG_ERR_CAPACITY, "an object outgrew its page cells past the histogram budget");
+      tab.npages[id] = np;
     }
   }
-  cells = (cells + 3) & ~uint64_t(3);
+  const uint64_t cells = tab.cur.cells = tab.cur.padded_cells();
   // id-indexed counters, re-laid out for newE entries
-  const uint64_t n_sum = 2 * kGlobalSums + (uint64_t)newE * 4 +
-                         ((h->flags & NMG_F_OBJECT_LEVELS) ? (uint64_t)newE * 2 * kLevelWords : 0);
-  const uint64_t n_min = 36 + (uint64_t)newE + 1;
+  const uint64_t n_sum = sum64_words(newE, levels), n_min = min64_words(newE);
   DevBuf<uint64_t> sum, mn, skeys;
   DevBuf<uint32_t> hist, svals, sdirty;
   DevBuf<unsigned long long> pk;
   DevBuf<DevEntry> ent;
-  const bool new_sparse = nsparse0 == 0 && !h->sparse_entries.empty() && !h->cnt.d_sparse_keys;
+  const bool new_sparse = cur0.nsparse == 0 && tab.cur.nsparse && !h->cnt.d_sparse_keys;
   // (the new arrays are released on return, after the copies into them have drained)
   auto undo = [&](hipError_t e, const char* what) {
     (void)hipStreamSynchronize(h->stream);
@@ -631,18 +557,23 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
         (e = hipMemsetAsync(sdirty, 0, 2 * 4, st)) != hipSuccess)
       return undo(e, "sparse page table");
   }
+  // the global words as they are, the count/weight rows with the new stride,
+  // the level rows and ordinals behind them, the error word at its new place
+  const uint64_t* osum = h->cnt.d_sum64;
+  const uint64_t* omin = h->cnt.d_min64;
   if ((e = hipMemsetAsync(sum, 0, n_sum * 8, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(sum, h->cnt.d_sum64, 2 * kGlobalSums * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
-      (oldE && (e = hipMemcpy2DAsync(sum + 2 * kGlobalSums, (size_t)newE * 8, h->cnt.d_sum64 + 2 * kGlobalSums,
-                                     (size_t)oldE * 8, (size_t)oldE * 8, 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
-      ((h->flags & NMG_F_OBJECT_LEVELS) && oldE &&
-       (e = hipMemcpyAsync(sum + 2 * kGlobalSums + (uint64_t)newE * 4, h->cnt.d_sum64 + 2 * kGlobalSums + (uint64_t)oldE * 4,
-                           (size_t)oldE * 2 * kLevelWords * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
+      (e = hipMemcpyAsync(sum, osum, kCwBase * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+      (oldE && (e = hipMemcpy2DAsync(sum + kCwBase, (size_t)newE * 8, osum + kCwBase, (size_t)oldE * 8, (size_t)oldE * 8,
+                                     kCwRows, hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
+      (levels && oldE &&
+       (e = hipMemcpyAsync(sum + levels_base(newE), osum + levels_base(oldE), (size_t)oldE * 2 * kLevelWords * 8,
+                           hipMemcpyDeviceToDevice, st)) != hipSuccess) ||
       (e = hipMemsetAsync(mn, 0xff, n_min * 8, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(mn, h->cnt.d_min64, (36 + (size_t)oldE) * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(mn + 36 + newE, h->cnt.d_min64 + 36 + oldE, 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(mn, omin, first_index(oldE) * 8, hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(mn + error_index(newE), omin + error_index(oldE), 8, hipMemcpyDeviceToDevice, st)) !=
+          hipSuccess ||
       (pk && (e = hipMemsetAsync(pk, 0, (size_t)newE * 2 * 8, st)) != hipSuccess) ||
-      (e = hipMemcpyAsync(ent, h->dev_entries.data(), (size_t)newE * sizeof(DevEntry), hipMemcpyHostToDevice, st)) !=
+      (e = hipMemcpyAsync(ent, tab.dev_entries.data(), (size_t)newE * sizeof(DevEntry), hipMemcpyHostToDevice, st)) !=
           hipSuccess)
     return undo(e, "re-layout");
   if (hist) {  // [thread][cell] rows with the new stride; moved entries' counts to their new range
@@ -650,10 +581,11 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
         (oldCells && (e = hipMemcpy2DAsync(hist, cells * 4, h->cnt.d_hist, oldCells * 4, oldCells * 4, T,
                                            hipMemcpyDeviceToDevice, st)) != hipSuccess))
       return undo(e, "page histogram re-layout");
-    for (const Move& m : moves)
-      if ((e = hipMemcpy2DAsync(hist + m.to, cells * 4, hist + m.from, cells * 4, m.np * 4, T, hipMemcpyDeviceToDevice,
-                                st)) != hipSuccess ||
-          (e = hipMemset2DAsync(hist + m.from, cells * 4, 0, m.np * 4, T, st)) != hipSuccess)
+    for (const Old& m : changed)  // (hist_base changed: a dense entry that moved)
+      if (m.hist != tab.hist_base[m.id] &&
+          ((e = hipMemcpy2DAsync(hist + tab.hist_base[m.id], cells * 4, hist + m.hist, cells * 4, m.np * 4, T,
+                                 hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+           (e = hipMemset2DAsync(hist + m.hist, cells * 4, 0, m.np * 4, T, st)) != hipSuccess))
         return undo(e, "page cells of a grown object");
   }
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return undo(e, "re-layout");
@@ -664,9 +596,7 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
   h->cnt.d_pk64 = std::move(pk);
   h->d_entries = std::move(ent);
   if (hist) h->cnt.d_hist = std::move(hist);
-  h->n_sum64 = n_sum;
-  h->n_min64 = n_min;
-  h->hist_cells = cells;
+  h->cnt.set_sizes(newE, levels);
   h->E = newE;
   if (new_sparse) {
     h->cnt.d_sparse_keys = std::move(skeys);
@@ -703,7 +633,7 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
       const uint32_t id = entry_ids[j];
       if (seen[id]) return fail(h, NMG_ERR_INVALID, "an entry id listed twice in one table");
       seen[id] = 1;
-      if (id < h->E && objects[j].buffer_size / kPageSize + 1 > h->npages[id]) nb_grown++;
+      if (id < h->E && objects[j].buffer_size / kPageSize + 1 > h->tab.npages[id]) nb_grown++;
     }
     for (uint32_t id = h->E; id < newE; id++)
       if (!seen[id]) return fail(h, NMG_ERR_RANGE, "new entry ids must be consecutive from the current entry count");
@@ -725,17 +655,7 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
     if (rc) return rc;
   }
   std::vector<DevEntry> chain(n);
-  for (uint32_t j = 0; j < n; j++) {
-    const uint32_t id = entry_ids[j];
-    const nmg_object& o = objects[j];
-    DevEntry& d = chain[j];
-    d = h->dev_entries[id];  // hist, sidx, id
-    d.addr = o.buffer_addr;
-    d.end = o.buffer_addr + o.buffer_size;
-    d.alloc = o.alloc_date;
-    d.free = o.free_date;
-    d.count = d.first = 0;
-  }
+  for (uint32_t j = 0; j < n; j++) chain[j] = h->tab.dev_entry(entry_ids[j], objects[j]);
   h->rt = RouteTable();  // (the partitions describe the previous table)
   // build the alarm's lookup beside the current one; keep the current one if that fails
   LookupSet next;
@@ -750,12 +670,7 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
   // the report's view: every listed entry as this table lists it, and this
   // table's order when it lists every entry (ma_finalize walks the table it
   // has at exit, FOREACH_HASH, mem_analyzer.c:1381-1383)
-  for (uint32_t j = 0; j < n; j++) {
-    const uint32_t id = entry_ids[j];
-    h->objects[id] = objects[j];
-    h->buffer_size[id] = objects[j].buffer_size;
-    h->entry_addr[id] = objects[j].buffer_addr;
-  }
+  for (uint32_t j = 0; j < n; j++) h->tab.describe(entry_ids[j], objects[j]);
   if (n == h->E) {
     bool identity = true;
     for (uint32_t j = 0; j < n && identity; j++) identity = entry_ids[j] == j;

@@ -27,6 +27,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .results import CW_ROWS, GLOBAL_SUM_WORDS, min64_words, sum64_words  # the counter arrays' layout
+
 INT64_MIN = -(1 << 63)
 
 
@@ -151,11 +153,6 @@ class HistPacker:
         return self.cells + nmax * 8
 
 
-GLOBAL_SUM_WORDS = 2 * 39  # sum64's head: [2 access][39] global sums (nmg_internal.h kGlobalSums)
-LEVEL_WORDS = 37           # per entry and access: na, 18 x (count, sum) (nmg_internal.h kLevelWords)
-GLOBAL_MIN_WORDS = 2 * 18  # min64's head: [2][18] bucket minima, then [E] ordinals and the error word
-
-
 class ObjPacker:
     """Buffers of the packed per-object counter merge of one engine
     (nmg_objcw_pack / nmg_objcw_unpack): sum64's four count / weight rows as
@@ -171,15 +168,15 @@ class ObjPacker:
         self.eng = eng
         n = eng.array_size(_lib.NMG_ARR_SUM64)
         levels = bool(eng.flags & _lib.NMG_F_OBJECT_LEVELS)
-        per = 4 + (2 * LEVEL_WORDS if levels else 0)  # (levels: [E][2][37] after the rows)
-        # the entry count from min64 ([2][18] minima, [E] ordinals, error word), checked
-        # against sum64's size: a layout change in nmg_internal.h fails here, not silently
-        self.E = eng.array_size(_lib.NMG_ARR_MIN64) - GLOBAL_MIN_WORDS - 1 if n else 0
-        if n and self.E * per + GLOBAL_SUM_WORDS != n:
-            raise RuntimeError(f"ObjPacker: sum64 holds {n} words, not {GLOBAL_SUM_WORDS} + {per} x {self.E} entries")
+        # the entry count from min64's size, checked against sum64's: a layout
+        # change in nmg_internal.h that results.py misses fails here, not silently
+        self.E = eng.array_size(_lib.NMG_ARR_MIN64) - min64_words(0) if n else 0
+        if n and sum64_words(self.E, levels) != n:
+            raise RuntimeError(f"ObjPacker: sum64 holds {n} words, not the {sum64_words(self.E, levels)} of "
+                               f"{self.E} entries")
         self.n_sum64 = n  # the engine's sum64 size this packer was built for
         self.levels = levels
-        self.rows = 4 * self.E
+        self.rows = CW_ROWS * self.E
         self.cap = max(1024, int(self.rows * ovf_frac))
         self.u32 = torch.empty(max(self.rows, 1), dtype=torch.int32, device=device)
         self.ovf = torch.empty(2 * self.cap, dtype=torch.int64, device=device)

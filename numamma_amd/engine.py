@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .replay import ObjectTable, Replay
+from .results import LEVEL_WORDS
 
 
 def _ptr(a: np.ndarray, ctype):
@@ -23,7 +24,7 @@ def _ptr(a: np.ndarray, ctype):
 
 
 def counters_to_numpy(c: "_lib.nmg_mem_counters") -> np.ndarray:
-    """struct mem_counters -> u64[75] (total_count, total_weight, na, 18 x (count, min, max, sum))."""
+    """struct mem_counters -> u64[COUNTER_WORDS] (total_count, total_weight, na, NB_BUCKETS x (count, min, max, sum))."""
     return np.frombuffer(bytes(c), dtype="<u8").copy()
 
 
@@ -253,7 +254,7 @@ class Engine:
 
     def object_levels(self):
         E = max(self.table.nb_entries, self.nb_entries)
-        lv = np.zeros((E, 2, 37), dtype=np.uint64)
+        lv = np.zeros((E, 2, LEVEL_WORDS), dtype=np.uint64)
         self._c(lib.nmg_get_object_levels(self.h, _ptr(lv, C.c_uint64)))
         return lv
 

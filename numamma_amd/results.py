@@ -4,11 +4,11 @@ Both the engine (nmg_run_replay(..., raw_path)) and the test oracle write
 this format, so parity checks compare every counter bit for bit:
 
     "NMGRES01", u32 nb_entries, u32 nb_buffers, u32 nb_threads, u32 0
-    u64 global[2][75]          struct mem_counters x {read, write}
+    u64 global[2][COUNTER_WORDS]  struct mem_counters x {read, write}
     u64 nb_samples_total, u64 nb_found_total
     u32 buf_samples[B], u32 buf_found[B]
-    u64 entry[E][79]           first-match ordinal, then per access:
-                               count, weight, na_miss_count, 18 x (count, sum)
+    u64 entry[E][ENTRY_WORDS]  first-match ordinal, then per access GLOBAL_SUMS words:
+                               count, weight, na_miss_count, NB_BUCKETS x (count, sum)
     u64 n, u32 cells[n][4]     (entry, thread, page, read+write count),
                                (entry, thread, page) order, non-zero only
 """
@@ -20,18 +20,44 @@ from typing import Optional
 
 import numpy as np
 
+# The engine's flat counter arrays (nmg_export_array), in u64 words: the Python
+# mirror of the layout in numamma_amd/csrc/nmg_internal.h, which describes it.
+# tests/test_layout_host.py compares every name here with the C++ one.
+NB_BUCKETS = 18                       # NMG_NB_BUCKETS / kBuckets: 9 hit + 9 miss levels
+GLOBAL_SUMS = 3 + 2 * NB_BUCKETS      # kGlobalSums: total_count, total_weight, na, NB_BUCKETS x (count, sum)
+LEVEL_WORDS = 1 + 2 * NB_BUCKETS      # kLevelWords, per entry and access: na, NB_BUCKETS x (count, sum)
+GLOBAL_SUM_WORDS = 2 * GLOBAL_SUMS    # kCwBase: sum64's head, [2 access][GLOBAL_SUMS]
+CW_ROWS = 4                           # kCwRows: then [2 access][2][E] count / weight rows
+GLOBAL_MIN_WORDS = 2 * NB_BUCKETS     # kGlobalMinMax: min64's head and all of max64, [2 access][NB_BUCKETS]
+COUNTER_WORDS = 3 + 4 * NB_BUCKETS    # struct mem_counters: ... NB_BUCKETS x (count, min, max, sum)
+ENTRY_WORDS = 1 + 2 * GLOBAL_SUMS     # the raw dump's record of one entry
+
+
+def sum64_words(nb_entries: int, levels: bool) -> int:
+    """sum64: the global sums, the rows, then [E][2][LEVEL_WORDS] with NMG_F_OBJECT_LEVELS."""
+    return GLOBAL_SUM_WORDS + nb_entries * (CW_ROWS + (2 * LEVEL_WORDS if levels else 0))
+
+
+def min64_words(nb_entries: int) -> int:
+    """min64: the global minima, [E] first-match ordinals, the error word."""
+    return GLOBAL_MIN_WORDS + nb_entries + 1
+
+
+def max64_words() -> int:
+    return GLOBAL_MIN_WORDS
+
 
 @dataclass
 class RawResults:
     nb_entries: int
     nb_buffers: int
     nb_threads: int
-    global_counters: np.ndarray  # u64[2][75]
+    global_counters: np.ndarray  # u64[2][COUNTER_WORDS]
     nb_samples: int
     nb_found: int
     buf_samples: np.ndarray
     buf_found: np.ndarray
-    entries: np.ndarray  # u64[E][79]
+    entries: np.ndarray  # u64[E][ENTRY_WORDS]
     cells: np.ndarray  # u32[n][4]
 
     @staticmethod
@@ -41,16 +67,16 @@ class RawResults:
             raise ValueError("not a raw-results dump")
         E, B, T, _ = np.frombuffer(raw, "<u4", 4, 8)
         off = 24
-        g = np.frombuffer(raw, "<u8", 150, off).reshape(2, 75).copy()
-        off += 1200
+        g = np.frombuffer(raw, "<u8", 2 * COUNTER_WORDS, off).reshape(2, COUNTER_WORDS).copy()
+        off += 8 * 2 * COUNTER_WORDS
         ns, nf = np.frombuffer(raw, "<u8", 2, off)
         off += 16
         bs = np.frombuffer(raw, "<u4", B, off).copy()
         off += 4 * B
         bf = np.frombuffer(raw, "<u4", B, off).copy()
         off += 4 * B
-        ent = np.frombuffer(raw, "<u8", E * 79, off).reshape(E, 79).copy()
-        off += 8 * 79 * E
+        ent = np.frombuffer(raw, "<u8", E * ENTRY_WORDS, off).reshape(E, ENTRY_WORDS).copy()
+        off += 8 * ENTRY_WORDS * E
         (n,) = np.frombuffer(raw, "<u8", 1, off)
         off += 8
         cells = np.frombuffer(raw, "<u4", 4 * int(n), off).reshape(int(n), 4).copy()
@@ -65,8 +91,8 @@ class RawResults:
         cw = np.zeros((self.nb_entries, 2, 2), dtype=np.uint64)
         cw[:, 0, 0] = self.entries[:, 1]
         cw[:, 0, 1] = self.entries[:, 2]
-        cw[:, 1, 0] = self.entries[:, 1 + 39]
-        cw[:, 1, 1] = self.entries[:, 2 + 39]
+        cw[:, 1, 0] = self.entries[:, 1 + GLOBAL_SUMS]
+        cw[:, 1, 1] = self.entries[:, 2 + GLOBAL_SUMS]
         return cw
 
 

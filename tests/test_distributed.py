@@ -34,7 +34,7 @@ def _worker(rank, world, port, workdir, ret):
     import pyoracle
     from numamma_amd.distributed import gather_arrays, merge_sparse, reduce_u64, shard_ranges
     from numamma_amd.replay import Replay, SynthConfig, generate
-    from numamma_amd.results import RawResults
+    from numamma_amd.results import COUNTER_WORDS, ENTRY_WORDS, GLOBAL_MIN_WORDS, NB_BUCKETS, RawResults
 
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     rp = generate(SynthConfig(nb_samples=60_000, nb_intervals=700, lost_frac=1e-3, seed=21))
@@ -52,7 +52,7 @@ def _worker(rank, world, port, workdir, ret):
     first[m] += np.uint64(lo) << np.uint64(32)  # shard-local -> global analysis position
 
     # the three u64 arrays, as an engine exports them
-    g = raw.global_counters  # [2][75]: tc, tw, na, 18 x (count, min, max, sum)
+    g = raw.global_counters  # [2][COUNTER_WORDS]: tc, tw, na, NB_BUCKETS x (count, min, max, sum)
     sums = [g[a, 0:3] for a in range(2)] + [np.stack([g[a, 3:][0::4], g[a, 3:][3::4]], axis=1).reshape(-1)
                                             for a in range(2)]
     sum64 = np.concatenate(sums + [raw.entries[:, 1:].reshape(-1)])
@@ -68,20 +68,20 @@ def _worker(rank, world, port, workdir, ret):
         s = t["sum"].numpy().view(np.uint64)
         mn = t["min"].numpy().view(np.uint64)
         mx = t["max"].numpy().view(np.uint64)
-        glob = np.zeros((2, 75), dtype=np.uint64)
+        glob = np.zeros((2, COUNTER_WORDS), dtype=np.uint64)
         off = 0
         for a in range(2):
             glob[a, 0:3] = s[off:off + 3]
             off += 3
         for a in range(2):
-            glob[a, 3:][0::4] = s[off:off + 36][0::2]
-            glob[a, 3:][3::4] = s[off:off + 36][1::2]
-            off += 36
-            glob[a, 3:][1::4] = mn[18 * a:18 * a + 18]
-            glob[a, 3:][2::4] = mx[18 * a:18 * a + 18]
-        ent = np.zeros((E, 79), dtype=np.uint64)
-        ent[:, 1:] = s[off:].reshape(E, 78)
-        ent[:, 0] = mn[36:]
+            glob[a, 3:][0::4] = s[off:off + 2 * NB_BUCKETS][0::2]
+            glob[a, 3:][3::4] = s[off:off + 2 * NB_BUCKETS][1::2]
+            off += 2 * NB_BUCKETS
+            glob[a, 3:][1::4] = mn[NB_BUCKETS * a:NB_BUCKETS * a + NB_BUCKETS]
+            glob[a, 3:][2::4] = mx[NB_BUCKETS * a:NB_BUCKETS * a + NB_BUCKETS]
+        ent = np.zeros((E, ENTRY_WORDS), dtype=np.uint64)
+        ent[:, 1:] = s[off:].reshape(E, ENTRY_WORDS - 1)
+        ent[:, 0] = mn[GLOBAL_MIN_WORDS:]
         # cells: merge as sparse (entry, thread, page) keys
         keys = [((c[:, 0].astype(np.uint64) << np.uint64(42)) | (c[:, 1].astype(np.uint64) << np.uint64(32))
                  | c[:, 2].astype(np.uint64), c[:, 3]) for c in cells]

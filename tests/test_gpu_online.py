@@ -345,3 +345,75 @@ def test_online_route_matches_single_pass():
     assert a[2] > 0
     for x, y in zip(a, b):
         assert np.array_equal(np.asarray(x), np.asarray(y))
+
+
+@pytest.mark.parametrize("flags", [_lib.NMG_F_DEFAULT, _lib.NMG_F_DEFAULT | _lib.NMG_F_OBJECT_LEVELS],
+                         ids=["plain", "levels"])
+def test_update_creates_first_sparse_entry(tmp_path, flags):
+    """A live host whose page-histogram budget the first alarm's table fills
+    exactly: every object of that table gets dense cells, and the objects
+    created by the second alarm are the engine's first sparse entries (the
+    sparse cell table is allocated by that nmg_update_objects, the counter
+    arrays re-laid out beside it).  Against the oracle's alarm mode."""
+    from numamma_amd.engine import Engine, table_objects
+    from numamma_amd.replay import ObjectTable
+    from numamma_amd.results import GLOBAL_SUMS
+
+    d = str(tmp_path)
+    rp = generate(SynthConfig(nb_samples=20_000, nb_intervals=300, nb_threads=2, with_stack=False,
+                              buffer_records=250, seed=85))
+    rp.buffers.reverse()
+    final = rp.table
+    alarms = online_alarms(rp, 8)  # two alarms: an early one (the objects are created early), and the end
+    snaps = [(be,) + table_at(final, t) for be, t in (alarms[0], alarms[-1])]
+    n1 = snaps[0][3].shape[0]
+    assert 0 < n1 < snaps[1][3].shape[0]  # the second alarm brings new objects
+    path = os.path.join(d, "replay.bin")
+    rp.write(path)
+    odir = os.path.join(d, "oracle")
+    pyoracle.run(path, odir, os.path.join(d, "o.txt"), os.path.join(d, "o_raw.bin"), alarms=snaps)
+    raw = RawResults.read(os.path.join(d, "o_raw.bin"))
+
+    cid = _creation_ids(final)
+    assert np.array_equal(np.sort(cid[snaps[0][3]]), np.arange(n1))  # (ids in creation order: the first table's are 0 .. n1 - 1)
+    cells1 = int((snaps[0][4][:, 1] // 4096 + 1).sum())
+    eng = Engine(flags=flags, nb_threads=rp.nb_threads, hist_budget_bytes=cells1 * rp.nb_threads * 4)
+    eng.set_objects(ObjectTable.empty())
+    eng.stream_begin(chunk_bytes=256 << 10, copy_threads=1)
+    b0 = 0
+    for be, keys, off, ids, ent4 in snaps:
+        eng.update_objects(keys, off, cid[ids], _ent_objs(ent4))
+        for b in rp.buffers[b0:be]:
+            eng.submit_ring(b.ring, b.data_tail, b.data_head, b.thread_rank, b.access_type)
+        b0 = be
+    eng.analyze()
+    eng.stream_end()
+    eng.synchronize()
+    eng.update_objects(final.keys, final.entry_off, cid, table_objects(final))  # ma_finalize's table
+    eng.table = final
+    # the dense arena is the first table's (padded to 4 cells per thread): nothing later got dense cells
+    assert eng.array_size(_lib.NMG_ARR_HIST32) == (cells1 + 3) // 4 * 4 * rp.nb_threads
+    g, ns, nf = eng.global_counters()
+    assert np.array_equal(g, raw.global_counters) and (ns, nf) == (raw.nb_samples, raw.nb_found)
+    s, f = eng.buffer_counts()
+    assert np.array_equal(s, raw.buf_samples) and np.array_equal(f, raw.buf_found)
+    first, cw = eng.object_counters()
+    assert np.array_equal(first[cid], raw.first_ordinal)
+    assert np.array_equal(cw[cid], raw.count_weight)
+    cells = eng.page_cells().copy()
+    assert (cells[:, 0] < n1).any() and (cells[:, 0] >= n1).any()  # dense and sparse entries both counted pages
+    pos = np.empty_like(cid)
+    pos[cid] = np.arange(cid.shape[0], dtype=np.uint32)
+    cells[:, 0] = pos[cells[:, 0]]
+    cells = cells[np.lexsort((cells[:, 2], cells[:, 1], cells[:, 0]))]
+    assert np.array_equal(cells, raw.cells)
+    if flags & _lib.NMG_F_OBJECT_LEVELS:
+        G = GLOBAL_SUMS  # the raw dump's entry record: first, then per access count, weight and the level words
+        want = np.stack([raw.entries[:, 1 + G * a + 2:1 + G * a + G] for a in range(2)], axis=1)
+        assert want.sum() > 0
+        assert np.array_equal(eng.object_levels()[cid], want)
+    edir = os.path.join(d, "engine")
+    eng.report(edir, os.path.join(d, "e.txt"), online=True)
+    eng.close()
+    assert open(os.path.join(d, "o.txt"), "rb").read() == open(os.path.join(d, "e.txt"), "rb").read()
+    _same_dirs(odir, edir)

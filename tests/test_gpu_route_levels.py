@@ -5,8 +5,9 @@ Large tables (> 1023 keys) take route2_kernel + local_kernel with these flags
 too; every test here drives Engine directly and asserts route_count() > 0, so
 it checks the route kernels and not attribute_kernel (NMG_F_SINGLE_PASS is the
 one variant that must report 0).  The reference is the oracle, whose raw dump
-holds entry[E][79]: ent[:, 1 + 39 * a + 2 : 1 + 39 * a + 39] is
-object_levels()[:, a, :] (na_miss, then 18 x (count, sum)).
+holds entry[E][ENTRY_WORDS] (numamma_amd/results.py): with G = GLOBAL_SUMS,
+ent[:, 1 + G * a + 2 : 1 + G * a + G] is object_levels()[:, a, :] (na_miss,
+then NB_BUCKETS x (count, sum)).
 
 Sizes are the smallest that reach each mechanism: two or three partitions of
 ~100k records (several 1023-chunk work items per partition: the atomic flush),

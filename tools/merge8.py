@@ -123,10 +123,12 @@ def _worker(rank, world, port, shm, args, ret):
 def merge_restatements(raws, seq_bases):
     """The merge algebra over per-shard raw results (numamma_amd/results.py
     layout): what the product's reduce chain must give."""
-    g = np.zeros((2, 75), dtype=np.uint64)
-    mins = np.zeros(75, dtype=bool)
-    maxs = np.zeros(75, dtype=bool)
-    for b in range(18):  # struct count {count, min_weight, max_weight, sum_weight} (mem_analyzer.h:10-15)
+    from numamma_amd.results import COUNTER_WORDS, NB_BUCKETS
+
+    g = np.zeros((2, COUNTER_WORDS), dtype=np.uint64)
+    mins = np.zeros(COUNTER_WORDS, dtype=bool)
+    maxs = np.zeros(COUNTER_WORDS, dtype=bool)
+    for b in range(NB_BUCKETS):  # struct count {count, min_weight, max_weight, sum_weight} (mem_analyzer.h:10-15)
         mins[3 + 4 * b + 1] = True
         maxs[3 + 4 * b + 2] = True
     sums = ~(mins | maxs)
