@@ -315,6 +315,43 @@ int64_t nmg_count_page_cells(nmg_engine *h);
 /* non-zero cells as (entry, thread, page, count) rows in (entry, thread, page) order */
 int nmg_get_page_cells(nmg_engine *h, uint32_t *rows /* [n][4] */, int64_t n);
 
+/* ---- access timeline: per selected object, u32 counters [time bin][thread][row]
+ * of its matched samples, a row being 2^row_shift consecutive 4 KiB pages.
+ * Counted on the device by every analysis (batch, streamed chunks, online
+ * alarms) next to the page histogram, cleared by nmg_reset_counters.
+ * A sample's bin: 0 for ts < t0, else min((ts - t0) >> bin_shift, nb_bins - 1);
+ * the clamp keeps every matched sample of a selected entry in exactly one
+ * cell, so the cells summed over the bins are the entry's page cells grouped
+ * by row.  An entry is selected when its page histogram is dense (huge ranges
+ * such as [stack] are not) and its buffer_size >= min_object_bytes; it takes
+ * nb_bins * nb_threads * R cells, R = (buffer_size / 4096 + 1 + 2^row_shift - 1)
+ * >> row_shift, at most 2^32 - 1 cells in all.
+ * nmg_set_timeline lays the cells out and zeroes them: after nmg_set_objects,
+ * on a single-GPU engine created with NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST,
+ * with no stream open (NMG_ERR_STATE otherwise; NMG_ERR_INVALID for options
+ * out of range, a multi-GPU handle or an engine without the two flags;
+ * NMG_ERR_CAPACITY, with the bytes needed in the error detail, when the cells
+ * exceed budget_bytes).  tl == NULL drops the timeline; so does a later
+ * nmg_set_objects.  With a timeline set, nmg_update_objects accepts only
+ * tables whose ids all exist already with the buffer_size they had at layout
+ * time (NMG_ERR_STATE otherwise, nothing changed): a live host whose table
+ * grows between alarms cannot keep a timeline yet.
+ * The getters (NMG_ERR_STATE without a timeline) return the non-zero cells as
+ * (entry, bin, thread, row, count) rows sorted by (entry, bin, thread, row),
+ * compacted on the device. */
+struct nmg_timeline_options {
+  uint64_t t0;               /* start of bin 0 (sample timestamp units, ns) */
+  uint32_t bin_shift;        /* a bin is 2^bin_shift ns (<= 63) */
+  uint32_t nb_bins;          /* 1..4096 */
+  uint32_t row_shift;        /* a row is 2^row_shift pages (<= 20) */
+  uint32_t reserved;         /* 0 */
+  uint64_t min_object_bytes; /* entries with buffer_size below it get no timeline */
+  uint64_t budget_bytes;     /* cap on the cell array (0: default 1 GiB) */
+};
+int nmg_set_timeline(nmg_engine *h, const struct nmg_timeline_options *tl);
+int64_t nmg_count_timeline_cells(nmg_engine *h);
+int nmg_get_timeline_cells(nmg_engine *h, uint32_t *rows /* [n][5] */, int64_t n);
+
 /* ---- results snapshot: the getters' results copied to host memory while
  * the next analysis runs (one engine of one GPU; not a multi-GPU handle, not
  * after nmg_set_buffer_counts).
@@ -441,6 +478,26 @@ struct nmg_host_results {
 };
 int nmg_report_host(const struct nmg_host_results *res, const struct nmg_object_meta *meta,
                     const struct nmg_report_options *opts, const char *stdout_path);
+
+/*
+ * The timeline per call site: one callsite_timeline_<id>.dat in
+ * opts->output_dir for every call site with a non-zero cell, <id> being the id
+ * nmg_report gives the site for the same results (opts->online as there).
+ * A header line "#thread_rank timestamp offset count", then one line
+ * "<thread> <t0 + (bin << bin_shift)> <row << (12 + row_shift)> <count>" per
+ * non-zero cell in (bin, thread, row) order, a site's cell being the sum of
+ * its objects' cells; the reference's plot_timeline reads the first three
+ * columns.  nmg_report_timeline downloads the engine's rows and calls the
+ * host function, which needs no GPU: res as for nmg_report_host (cells are
+ * not read), tl the options the rows were counted with, rows as
+ * nmg_get_timeline_cells returns them.
+ */
+int nmg_report_timeline(nmg_engine *h, const struct nmg_object_meta *meta,
+                        const struct nmg_report_options *opts);
+int nmg_report_timeline_host(const struct nmg_host_results *res, const struct nmg_object_meta *meta,
+                             const struct nmg_report_options *opts,
+                             const struct nmg_timeline_options *tl,
+                             const uint32_t *rows, int64_t n);
 
 /* Convenience driver used by the nmg_replay CLI and the tests: load a replay
  * file (DESIGN.md "Replay format"), analyse it on `device`, report. */

@@ -143,6 +143,11 @@ class nmg_host_results(C.Structure):
     ]
 
 
+class nmg_timeline_options(C.Structure):
+    _fields_ = [("t0", C.c_uint64), ("bin_shift", C.c_uint32), ("nb_bins", C.c_uint32), ("row_shift", C.c_uint32),
+                ("reserved", C.c_uint32), ("min_object_bytes", C.c_uint64), ("budget_bytes", C.c_uint64)]
+
+
 class nmg_results_view(C.Structure):
     _fields_ = [
         ("global_", nmg_mem_counters * 2),
@@ -200,6 +205,13 @@ _SIGS = {
     "nmg_get_object_levels": (C.c_int, [H, u64p]),
     "nmg_count_page_cells": (C.c_int64, [H]),
     "nmg_get_page_cells": (C.c_int, [H, u32p, C.c_int64]),
+    "nmg_set_timeline": (C.c_int, [H, C.POINTER(nmg_timeline_options)]),
+    "nmg_count_timeline_cells": (C.c_int64, [H]),
+    "nmg_get_timeline_cells": (C.c_int, [H, u32p, C.c_int64]),
+    "nmg_report_timeline": (C.c_int, [H, C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options)]),
+    "nmg_report_timeline_host": (C.c_int, [C.POINTER(nmg_host_results), C.POINTER(nmg_object_meta),
+                                           C.POINTER(nmg_report_options), C.POINTER(nmg_timeline_options), u32p,
+                                           C.c_int64]),
     "nmg_results_begin": (C.c_int, [H]),
     "nmg_results_end": (C.c_int, [H, C.POINTER(nmg_results_view)]),
     "nmg_array_size": (C.c_uint64, [H, C.c_int]),

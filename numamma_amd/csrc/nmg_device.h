@@ -94,6 +94,45 @@ __device__ __forceinline__ void level_count(const Params& p, uint64_t e, uint32_
   }
 }
 
+// Access timeline (Params::tl): the cell of a matched SAMPLE with timestamp ts
+// (absolute), thread th and page `page` of an entry whose by-id record has
+// pad1 = pad (tl_pad).  Bin 0 before t0, the last bin from its start on.
+__device__ __forceinline__ uint32_t timeline_cell(const Params& p, uint64_t pad, uint64_t ts, uint32_t th,
+                                                  uint32_t page) {
+  const uint64_t d = ts < p.tl_t0 ? 0ull : (ts - p.tl_t0) >> p.tl_bin_shift;
+  const uint32_t bin = (uint32_t)min(d, (uint64_t)(p.tl_nb_bins - 1));
+  const uint32_t R = (uint32_t)(pad >> 32);
+  return (uint32_t)pad + (bin * p.nb_threads + th) * R + (page >> p.tl_row_shift);
+}
+
+// One add per lane with `on` into its timeline cell (no-return u32 global
+// atomics).  It ballots the lanes that reach it, so it may be called from a
+// diverged region (process_sample calls it past its early returns; the
+// extras block of local_kernel at a wave-uniform point): the lanes present
+// run the rounds together, the others take no part.  A chunk's records of a
+// hot object share entry and thread and mostly the bin: per round, the lanes
+// whose cell equals the first pending lane's leave together and that lane
+// adds their number.  They differ in row, so the rounds are bounded
+// (`rounds`: Params::tl_rounds); the lanes still pending then add 1 each.
+// rounds = 0 is the single-lane add (direct_attribute: no cross-lane step).
+__device__ __forceinline__ void timeline_add(const Params& p, bool on, uint32_t cell, uint32_t rounds) {
+  if (rounds > 0) {
+    const uint32_t lane = __lane_id();
+    uint64_t todo = __ballot(on);
+#pragma unroll 1
+    for (uint32_t r = 0; r < rounds && todo; r++) {
+      const uint32_t lead = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(todo));
+      const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cell, (int)lead);
+      const bool same = on && cell == c;  // (all still pending: a cell's lanes leave together)
+      const uint64_t sm = __ballot(same);
+      if (lane == lead) atomicAdd(p.tl + cell, (uint32_t)__popcll(sm));
+      on = on && !same;
+      todo &= ~sm;
+    }
+  }
+  if (on) atomicAdd(p.tl + cell, 1u);
+}
+
 __device__ __forceinline__ void set_error(const Params& p, uint64_t seq, uint32_t off, uint32_t code) {
   uint64_t w = (seq << 40) | (uint64_t(off) << 8) | code;
   atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + p.nb_entries),

@@ -272,6 +272,7 @@ extern "C" int nmg_reset_counters(nmg_engine* h) {
   const uint64_t longest = std::max<uint64_t>({r.n_hist16, r.n_sum64, r.n_min64, r.sparse_cap, r.n_bufcnt, 1});
   const uint32_t rgrid = (uint32_t)std::min<uint64_t>((longest + 256 * 16 - 1) / (256 * 16), (uint64_t)h->num_cus * 4);
   HIP_TRY(h, launch_reset(rgrid, h->stream, r));
+  if (h->tl.on) HIP_TRY(h, hipMemsetAsync(h->tl.d_cells, 0, h->tl.ncells * 4, h->stream));
   h->nreset++;
   h->counters_fresh = true;
   return NMG_OK;
@@ -520,6 +521,54 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   }
   std::string err;
   rc = write_report(&res, meta, opts, stdout_path, err, dumps ? &dump : nullptr, &r.nb_found_total);
+  if (rc && !err.empty()) h->last_error = err;
+  return rc;
+}
+
+// The timeline rows and the counters the call-site registry needs, handed to
+// the host writer (entries in the report's walk order, as nmg_report).
+extern "C" int nmg_report_timeline(nmg_engine* h, const nmg_object_meta* meta, const nmg_report_options* opts) {
+  Range range("nmg_report_timeline");
+  if (!h || (h->E && !meta)) return NMG_ERR_INVALID;
+  if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_report_timeline before nmg_set_objects");
+  if (!h->tl.on) return fail(h, NMG_ERR_STATE, "no timeline set (nmg_set_timeline)");
+  HostResults r;
+  int rc = engine_download(h, r, true, false);
+  if (rc) return rc;
+  std::vector<uint32_t> rows;
+  int64_t n = 0;
+  rc = collect_timeline_cells(h, &rows, &n);
+  if (rc) return rc;
+  nmg_host_results res;
+  memset(&res, 0, sizeof(res));
+  res.nb_entries = h->E;
+  res.buffer_size = h->tab.buffer_size.data();
+  res.first_ordinal = r.first.data();
+  res.count_weight = r.count_weight.data();
+  res.nb_threads = h->T;
+  res.match_samples = 1;
+  std::vector<uint64_t> w_size, w_first, w_cw;
+  if (!h->order.empty()) {  // (live online tables: meta follows the walk order)
+    const uint32_t E = h->E;
+    if (h->order.size() != E) return fail(h, NMG_ERR_STATE, "report walk order does not cover every entry");
+    std::vector<uint32_t> pos(E);
+    w_size.resize(E);
+    w_first.resize(E);
+    w_cw.resize((size_t)E * 4);
+    for (uint32_t k = 0; k < E; k++) {
+      const uint32_t id = h->order[k];
+      pos[id] = k;
+      w_size[k] = h->tab.buffer_size[id];
+      w_first[k] = r.first[id];
+      for (int q = 0; q < 4; q++) w_cw[(size_t)k * 4 + q] = r.count_weight[(size_t)id * 4 + q];
+    }
+    for (int64_t i = 0; i < n; i++) rows[5 * i] = pos[rows[5 * i]];  // (the writer groups by site: any order)
+    res.buffer_size = w_size.data();
+    res.first_ordinal = w_first.data();
+    res.count_weight = w_cw.data();
+  }
+  std::string err;
+  rc = write_timeline(&res, meta, opts, &h->tl.opt, rows.data(), n, err);
   if (rc && !err.empty()) h->last_error = err;
   return rc;
 }

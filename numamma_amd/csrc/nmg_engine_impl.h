@@ -247,6 +247,24 @@ struct CellLayout {
   int ensure(nmg_engine* h, uint64_t E, uint64_t nsent);  // (re)allocated when the table outgrows them
 };
 
+// The access timeline (nmg_set_timeline): the cell array, the selected entries
+// in id order (their cells lie in that order; each entry's base and rows are
+// also in its DevEntry::pad1, tl_pad) and the getters' work arrays.
+struct Timeline {
+  bool on = false;
+  nmg_timeline_options opt{};
+  uint64_t ncells = 0;
+  uint32_t rounds = kTlRounds;  // Params::tl_rounds
+  DevBuf<uint32_t> d_cells;
+  std::vector<uint32_t> ids, base, nrows;  // base has one more: ncells
+  DevBuf<uint32_t> d_ids, d_base, d_nrows;
+  // rows of the current results epoch (nmg_count_timeline_cells, then the copy out)
+  DevBuf<uint32_t> d_cnt, d_rows;
+  DevBuf<uint64_t> d_off, d_part;
+  uint64_t rows_epoch = 0;
+  int64_t n = 0;
+};
+
 struct nmg_engine {
   int device = 0;
   uint32_t flags = NMG_F_DEFAULT;
@@ -323,6 +341,7 @@ struct nmg_engine {
   DevBuf<unsigned long long> d_found;  // matched SAMPLEs since the last reset (Params::found)
   DevBuf<uint64_t> d_scratch;          // [2] small device results (nmg_hist_pack / unpack) + range counts
   DevBuf<uint32_t> d_smatch;           // NMG_F_SAMPLE_MATCHES: per 8 B of the arena span
+  Timeline tl;                         // nmg_set_timeline (dropped with the table)
   uint64_t nreset = 0;
 
   // buffers
@@ -506,6 +525,8 @@ int decode_error_word(nmg_engine* h, uint64_t w);
 int cells_prepare(nmg_engine* h);
 int cells_fill(nmg_engine* h, uint32_t* rows);
 int collect_page_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);
+int timeline_prepare(nmg_engine* h);
+int collect_timeline_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);  // [n][5]
 void* array_ptr(nmg_engine* h, int which, size_t* bytes);
 int scratch_u64(nmg_engine* h);
 int sparse_nonempty(nmg_engine* h, bool* out);

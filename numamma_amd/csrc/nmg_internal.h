@@ -157,5 +157,8 @@ struct DumpInput {
 int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
                  const char* stdout_path, std::string& err, const DumpInput* dump = nullptr,
                  const uint64_t* found_total = nullptr);
+// callsite_timeline_<id>.dat files from (entry, bin, thread, row, count) rows
+int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
+                   const nmg_timeline_options* tl, const uint32_t* rows, int64_t n, std::string& err);
 
 }  // namespace nmg

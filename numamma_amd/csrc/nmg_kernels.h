@@ -165,7 +165,30 @@ struct Params {
   uint4* tlog;               // [grid][tlog_parts][tlog_cap] 16 B slots (kTlogHead layouts); null: off
   uint32_t* tlog_cnt;        // [grid][tlog_parts] records written
   uint32_t tlog_cap, tlog_rshift, tlog_parts;
+  // access timeline (nmg_set_timeline): u32 cells [bin][thread][row] per
+  // selected entry from the base in its DevEntry::pad1 (tl_pad); null: off
+  uint32_t* tl;
+  uint64_t tl_t0;
+  uint32_t tl_bin_shift, tl_nb_bins, tl_row_shift;
+  uint32_t tl_rounds;  // timeline_add's merge rounds (kTlRounds)
 };
+
+// DevEntry::pad1 of the by-id entries (Params::entries): the entry's first
+// timeline cell and its rows R, or kTlNone (no timeline, or the entry is not
+// selected).  Cell of (bin, thread, page) = base + (bin * nb_threads + thread) * R
+// + (page >> row_shift), below 2^32.
+constexpr uint64_t kTlNone = ~0ull;
+constexpr uint64_t tl_pad(uint32_t base, uint32_t rows) { return (uint64_t(rows) << 32) | base; }
+
+// merge rounds of timeline_add (nmg_device.h) before the remaining lanes add
+// their own cell: Params::tl_rounds, kTlRounds unless the environment variable
+// NMG_TL_ROUNDS (0..64) says otherwise when the timeline is set.  0 is an
+// atomic per record, the fastest at the configs[3] shard with 64 bins and
+// page rows (3.84 ms a step against 3.90 / 3.91 / 3.96 / 4.19 for 1 / 2 / 4 /
+// 16 rounds: the cells of a hot object spread over bins and rows).  Merging
+// pays only where the options put a hot object's records on one cell (one
+// bin, one row: 17.0 ms at 0 rounds, 14.1 ms at 4); DESIGN 7.0r8.
+constexpr uint32_t kTlRounds = 0;
 
 // tlog_reduce_kernel (long-tail log, see Params::tlog)
 struct TlogParams {
@@ -235,5 +258,16 @@ hipError_t launch_cells_count(hipStream_t s, const uint32_t* hist, uint64_t hist
                               const uint64_t* base, const uint32_t* np, uint32_t E, uint32_t* cnt);
 hipError_t launch_cells_emit(hipStream_t s, const uint32_t* hist, uint64_t hist_cells, uint32_t T,
                              const uint64_t* base, const uint32_t* np, uint32_t E, const uint64_t* off, uint4* rows);
+// timeline rows on the device (nmg_get_timeline_cells): the cell array in
+// segments of kTlSeg cells, per segment the number of non-zero cells, then
+// (after a scan) the (entry, bin, thread, row, count) rows at each segment's
+// offset.  The selected entries' cells lie in entry order, each entry's in
+// (bin, thread, row) order, so cell order is row order.  ids / base / nrows:
+// the n selected entries, base[n] = ncells.
+constexpr uint32_t kTlSeg = 2048;
+hipError_t launch_tl_count(hipStream_t s, const uint32_t* tl, uint64_t ncells, uint32_t* cnt);
+hipError_t launch_tl_emit(hipStream_t s, const uint32_t* tl, uint64_t ncells, const uint32_t* ids,
+                          const uint32_t* base, const uint32_t* nrows, uint32_t n, uint32_t T, const uint64_t* off,
+                          uint32_t* rows);
 
 }  // namespace nmg

@@ -361,6 +361,13 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
   }
   sub_stamp<TIMING>(st, 3);
   if (p.flags & NMG_F_OBJECT_LEVELS) level_count(p, uint64_t(e), access, lvl, w);
+  // access timeline: the matched lanes are the ones left here (the early
+  // returns above), and timeline_add ballots the lanes that reach it
+  if (p.tl) {
+    const uint64_t pad = p.entries[e].pad1;
+    const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
+    timeline_add(p, pad != kTlNone, timeline_cell(p, pad, ts, th, page), p.tl_rounds);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1444,6 +1451,81 @@ hipError_t launch_cells_emit(hipStream_t s, const uint32_t* hist, uint64_t hist_
   const uint32_t grid = (uint32_t)std::min<uint64_t>((E + 3) / 4, 8192);
   hipLaunchKernelGGL(cells_emit_kernel, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, hist, hist_cells, T,
                      base, np, E, off, rows);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Timeline rows (launch_tl_count / launch_tl_emit in nmg_kernels.h): one wave
+// per kTlSeg-cell segment, 64 consecutive cells per step; a ballot gives each
+// non-zero cell its row.  Reads stay below ncells.
+
+__global__ __launch_bounds__(256) void tl_count_kernel(const uint32_t* tl, uint64_t ncells, uint32_t nseg,
+                                                       uint32_t* cnt) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t nw = gridDim.x * (blockDim.x / 64);
+  for (uint32_t sg = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; sg < nseg; sg += nw) {
+    const uint64_t c0 = uint64_t(sg) * kTlSeg;
+    uint32_t n = 0;
+    for (uint32_t i0 = 0; i0 < kTlSeg; i0 += 64) {
+      const uint64_t c = c0 + i0 + lane;
+      n += (uint32_t)__popcll(__ballot(c < ncells && tl[c] != 0));
+    }
+    if (lane == 0) cnt[sg] = n;
+  }
+}
+
+__global__ __launch_bounds__(256) void tl_emit_kernel(const uint32_t* tl, uint64_t ncells, uint32_t nseg,
+                                                      const uint32_t* ids, const uint32_t* base, const uint32_t* nrows,
+                                                      uint32_t n, uint32_t T, const uint64_t* off, uint32_t* rows) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t nw = gridDim.x * (blockDim.x / 64);
+  for (uint32_t sg = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; sg < nseg; sg += nw) {
+    const uint64_t c0 = uint64_t(sg) * kTlSeg;
+    uint64_t o = off[sg];
+    for (uint32_t i0 = 0; i0 < kTlSeg; i0 += 64) {
+      const uint64_t c = c0 + i0 + lane;
+      const uint32_t v = c < ncells ? tl[c] : 0u;
+      const uint64_t m = __ballot(v != 0);
+      if (v) {
+        // the selected entry k with base[k] <= c < base[k + 1] (c < ncells = base[n])
+        uint32_t k = 0, len = n;
+        while (len > 1) {
+          const uint32_t half = len >> 1;
+          if ((uint64_t)base[k + half] <= c) {
+            k += half;
+            len -= half;
+          } else {
+            len = half;
+          }
+        }
+        const uint32_t R = nrows[k], rel = (uint32_t)(c - base[k]);
+        const uint32_t bt = rel / R, row = rel - bt * R, bin = bt / T, th = bt - bin * T;
+        uint32_t* r = rows + (o + __popcll(m & ((1ull << lane) - 1))) * 5;
+        r[0] = ids[k];
+        r[1] = bin;
+        r[2] = th;
+        r[3] = row;
+        r[4] = v;
+      }
+      o += (uint64_t)__popcll(m);
+    }
+  }
+}
+
+hipError_t launch_tl_count(hipStream_t s, const uint32_t* tl, uint64_t ncells, uint32_t* cnt) {
+  const uint32_t nseg = (uint32_t)((ncells + kTlSeg - 1) / kTlSeg);
+  const uint32_t grid = std::min<uint32_t>((nseg + 3) / 4, 8192);
+  hipLaunchKernelGGL(tl_count_kernel, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, tl, ncells, nseg, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_tl_emit(hipStream_t s, const uint32_t* tl, uint64_t ncells, const uint32_t* ids,
+                          const uint32_t* base, const uint32_t* nrows, uint32_t n, uint32_t T, const uint64_t* off,
+                          uint32_t* rows) {
+  const uint32_t nseg = (uint32_t)((ncells + kTlSeg - 1) / kTlSeg);
+  const uint32_t grid = std::min<uint32_t>((nseg + 3) / 4, 8192);
+  hipLaunchKernelGGL(tl_emit_kernel, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, tl, ncells, nseg, ids, base,
+                     nrows, n, T, off, rows);
   return hipGetLastError();
 }
 

@@ -417,7 +417,103 @@ int write_object_summary(const std::string& path, const nmg_host_results* r, con
   return NMG_OK;
 }
 
+// The call sites of the results r (settings.match_samples on), as ma_finalize
+// leaves them: created in the analysis order of each object's first matched
+// sample, then every object that reaches update_call_sites attached.  The one
+// registry of write_report and write_timeline: a site's id is the same in both.
+template <class Phase>
+int fill_registry(Registry& reg, const nmg_host_results* r, const nmg_object_meta* meta, bool online,
+                  std::string& err, Phase&& phase) {
+  const uint32_t E = r->nb_entries;
+  std::vector<uint32_t> matched;
+  for (uint32_t e = 0; e < E; e++)
+    if (r->first_ordinal[e] != ~0ull) matched.push_back(e);
+  // objects that reach update_call_sites: the matched ones, or every one online
+  std::vector<uint32_t> updated;
+  if (online)
+    for (uint32_t e = 0; e < E; e++) updated.push_back(e);
+  else
+    updated = matched;
+  for (uint32_t e : updated)
+    if (meta[e].callstack == nullptr && meta[e].callstack_size > 3) {
+      err = "entry with NULL callstack and callstack_size > 3 (the reference dereferences NULL)";
+      return NMG_ERR_INVALID;
+    }
+  // creation: in the analysis order of each object's first matched sample
+  std::vector<uint32_t> order(matched);
+  std::sort(order.begin(), order.end(),
+            [&](uint32_t a, uint32_t b) { return r->first_ordinal[a] < r->first_ordinal[b]; });
+  phase("registry: order");
+  for (uint32_t e : order)
+    if (reg.find(e) < 0) reg.create(e, r->buffer_size[e] / kPageSize + 1);
+  phase("registry: create");
+  // update_call_sites in FOREACH_HASH order (= flattened order); online, an
+  // object never matched finds or creates its site here
+  for (uint32_t e : updated) {
+    int si = reg.find(e);
+    if (si < 0) si = reg.create(e, r->buffer_size[e] / kPageSize + 1);
+    Site& site = reg.sites[si];
+    site.nb_mallocs++;
+    const uint64_t* cw = r->count_weight + (uint64_t)e * 4;
+    site.read_count += cw[0];
+    site.read_weight += cw[1];
+    site.write_count += cw[2];
+    site.write_weight += cw[3];
+    site.objects.push_back(e);
+  }
+  return NMG_OK;
+}
+
 }  // namespace
+
+// callsite_timeline_<id>.dat per call site with a non-zero cell (the format is
+// in include/numamma_gpu.h).  rows: (entry, bin, thread, row, count), any
+// order; a site's cell sums its objects' cells, as update_call_sites sums
+// their page blocks.  Stack objects have no per-site files (_dump_call_site,
+// mem_sampling.c:775-808).
+int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
+                   const nmg_timeline_options* tl, const uint32_t* rows, int64_t n, std::string& err) {
+  const bool online = opts && opts->online;
+  Registry reg(meta);
+  if (r->match_samples) {
+    const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
+    if (rc) return rc;
+  }
+  // per site: (bin, thread, row) key and count of every row of its objects
+  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> per(reg.sites.size());
+  for (int64_t i = 0; i < n; i++) {
+    const uint32_t* q = rows + 5 * i;
+    if (!q[4] || meta[q[0]].mem_type == kMemTypeStack) continue;
+    const int64_t si = reg.find(q[0]);
+    if (si < 0) continue;  // (an entry without matched samples has no cells)
+    per[si].push_back({(uint64_t(q[1]) << 42) | (uint64_t(q[2]) << 32) | q[3], q[4]});
+  }
+  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
+  mkdir(dir, S_IRWXU);
+  for (size_t si = 0; si < per.size(); si++) {
+    auto& l = per[si];
+    if (l.empty()) continue;
+    std::sort(l.begin(), l.end());
+    char fn[4096];
+    snprintf(fn, sizeof(fn), "%s/callsite_timeline_%d.dat", dir, (int)reg.sites[si].id);
+    FILE* f = fopen(fn, "w");
+    if (!f) {
+      err = std::string("cannot open ") + fn;
+      return NMG_ERR_IO;
+    }
+    fprintf(f, "#thread_rank timestamp offset count\n");
+    for (size_t i = 0; i < l.size();) {
+      const uint64_t key = l[i].first;
+      uint64_t cnt = 0;
+      for (; i < l.size() && l[i].first == key; i++) cnt += l[i].second;
+      const uint64_t bin = key >> 42, th = (key >> 32) & 0x3ff, row = key & 0xffffffffull;
+      fprintf(f, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", th, tl->t0 + (bin << tl->bin_shift),
+              row << (12 + tl->row_shift), cnt);
+    }
+    fclose(f);
+  }
+  return NMG_OK;
+}
 
 int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
                  const char* stdout_path, std::string& err, const DumpInput* dump, const uint64_t* found_override) {
@@ -476,43 +572,11 @@ int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const n
   // ---- call sites
   phase("buffers");
   Registry reg(meta);
-  std::vector<uint32_t> matched;
   if (r->match_samples) {
-    for (uint32_t e = 0; e < E; e++)
-      if (r->first_ordinal[e] != ~0ull) matched.push_back(e);
-    // objects that reach update_call_sites: the matched ones, or every one online
-    std::vector<uint32_t> updated;
-    if (online)
-      for (uint32_t e = 0; e < E; e++) updated.push_back(e);
-    else
-      updated = matched;
-    for (uint32_t e : updated)
-      if (meta[e].callstack == nullptr && meta[e].callstack_size > 3) {
-        close_out();
-        err = "entry with NULL callstack and callstack_size > 3 (the reference dereferences NULL)";
-        return NMG_ERR_INVALID;
-      }
-    // creation: in the analysis order of each object's first matched sample
-    std::vector<uint32_t> order(matched);
-    std::sort(order.begin(), order.end(),
-              [&](uint32_t a, uint32_t b) { return r->first_ordinal[a] < r->first_ordinal[b]; });
-    phase("registry: order");
-    for (uint32_t e : order)
-      if (reg.find(e) < 0) reg.create(e, r->buffer_size[e] / kPageSize + 1);
-    phase("registry: create");
-    // update_call_sites in FOREACH_HASH order (= flattened order); online, an
-    // object never matched finds or creates its site here
-    for (uint32_t e : updated) {
-      int si = reg.find(e);
-      if (si < 0) si = reg.create(e, r->buffer_size[e] / kPageSize + 1);
-      Site& site = reg.sites[si];
-      site.nb_mallocs++;
-      const uint64_t* cw = r->count_weight + (uint64_t)e * 4;
-      site.read_count += cw[0];
-      site.read_weight += cw[1];
-      site.write_count += cw[2];
-      site.write_weight += cw[3];
-      site.objects.push_back(e);
+    const int rc = fill_registry(reg, r, meta, online, err, phase);
+    if (rc) {
+      close_out();
+      return rc;
     }
   }
   std::vector<Site>& sites = reg.sites;
@@ -762,6 +826,23 @@ int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const n
 }
 
 }  // namespace nmg
+
+extern "C" int nmg_report_timeline_host(const nmg_host_results* res, const nmg_object_meta* meta,
+                                        const nmg_report_options* opts, const nmg_timeline_options* tl,
+                                        const uint32_t* rows, int64_t n) {
+  if (!res || !tl || n < 0 || (n && !rows) ||
+      (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight || !res->buffer_size)) ||
+      res->nb_threads > NMG_MAX_THREADS || tl->bin_shift > 63 || tl->nb_bins < 1 || tl->nb_bins > 4096 ||
+      tl->row_shift > 20 || tl->reserved != 0)
+    return NMG_ERR_INVALID;
+  for (int64_t i = 0; i < n; i++)
+    if (rows[5 * i] >= res->nb_entries || rows[5 * i + 1] >= tl->nb_bins || rows[5 * i + 2] >= res->nb_threads)
+      return NMG_ERR_INVALID;
+  std::string err;
+  int rc = nmg::write_timeline(res, meta, opts, tl, rows, n, err);
+  if (rc && !err.empty()) fprintf(stderr, "nmg_report_timeline: %s\n", err.c_str());
+  return rc;
+}
 
 extern "C" int nmg_report_host(const nmg_host_results* res, const nmg_object_meta* meta,
                                const nmg_report_options* opts, const char* stdout_path) {

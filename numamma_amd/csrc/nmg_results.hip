@@ -321,6 +321,62 @@ extern "C" int nmg_get_page_cells(nmg_engine* h, uint32_t* rows, int64_t n) {
   return n ? cells_fill(h, rows) : NMG_OK;
 }
 
+// ---- access timeline rows: counted per segment, scanned and emitted on the
+// device (the page cells' pattern); they stay there (tl.d_rows) until copied
+// out, cached per results epoch
+int timeline_prepare(nmg_engine* h) {
+  Timeline& t = h->tl;
+  if (!t.on) return fail(h, NMG_ERR_STATE, "no timeline set (nmg_set_timeline)");
+  if (t.rows_epoch == h->epoch) return NMG_OK;
+  int rc = nmg_synchronize(h);
+  if (rc) return rc;
+  uint64_t n = 0;
+  const uint64_t nseg = (t.ncells + kTlSeg - 1) / kTlSeg;
+  if (nseg) {
+    hipStream_t st = h->stream;
+    HIP_TRY(h, t.d_cnt.reserve(nseg));
+    HIP_TRY(h, t.d_off.reserve(nseg + 1));
+    HIP_TRY(h, t.d_part.reserve(scan_parts(nseg) + 1));
+    HIP_TRY(h, launch_tl_count(st, t.d_cells, t.ncells, t.d_cnt));
+    HIP_TRY(h, launch_scan_u32(st, t.d_cnt, nseg, t.d_off, t.d_part));
+    HIP_TRY(h, hipMemcpyAsync(&n, t.d_off + nseg, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (n) {
+      HIP_TRY(h, t.d_rows.reserve(n * 5));
+      HIP_TRY(h, launch_tl_emit(st, t.d_cells, t.ncells, t.d_ids, t.d_base, t.d_nrows, (uint32_t)t.ids.size(), h->T,
+                                t.d_off, t.d_rows));
+      HIP_TRY(h, hipStreamSynchronize(st));
+    }
+  }
+  t.n = (int64_t)n;
+  t.rows_epoch = h->epoch;
+  return NMG_OK;
+}
+
+int collect_timeline_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count) {
+  int rc = timeline_prepare(h);
+  if (rc) return rc;
+  *count = h->tl.n;
+  rows->resize((size_t)h->tl.n * 5);
+  if (h->tl.n) HIP_TRY(h, hipMemcpy(rows->data(), h->tl.d_rows, (size_t)h->tl.n * 20, hipMemcpyDeviceToHost));
+  return NMG_OK;
+}
+
+extern "C" int64_t nmg_count_timeline_cells(nmg_engine* h) {
+  if (!h) return NMG_ERR_INVALID;
+  int rc = timeline_prepare(h);
+  return rc ? rc : h->tl.n;
+}
+
+extern "C" int nmg_get_timeline_cells(nmg_engine* h, uint32_t* rows, int64_t n) {
+  if (!h || (n && !rows)) return NMG_ERR_INVALID;
+  int rc = timeline_prepare(h);
+  if (rc) return rc;
+  if (h->tl.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
+  if (n) HIP_TRY(h, hipMemcpy(rows, h->tl.d_rows, (size_t)n * 20, hipMemcpyDeviceToHost));
+  return NMG_OK;
+}
+
 // ---- multi-GPU merge support
 
 extern "C" uint64_t nmg_array_size(nmg_engine* h, int which) {

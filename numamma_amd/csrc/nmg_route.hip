@@ -95,7 +95,9 @@ __device__ __forceinline__ uint32_t raw_mem_lvl(const uint8_t* data, uint64_t po
 // only taken when a workgroup's samples outgrow its pool (SAMPLE records
 // shorter than 40 B, or the kDbgTinyPool test switch).  lvl = the record's
 // data_src.mem_lvl (read with NMG_F_OBJECT_LEVELS only); slot = its buffer's
-// index in p.sbufs (analysis order).
+// index in p.sbufs (analysis order).  TL: the caller's instance serves engines
+// with a timeline set (route2_kernel has one of each).
+template <bool TL>
 __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr, uint64_t ts, uint64_t w, uint32_t th,
                                                  uint32_t acc, uint32_t lvl, uint64_t seq, uint32_t off,
                                                  uint32_t slot) {
@@ -144,6 +146,10 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
   } else {
     const uint32_t sidx = p.entries[e].sidx;
     if (sidx != ~0u) sparse_add(p, sparse_key(sidx, th, page), seq, off, 1u);
+  }
+  if (TL && p.tl) {  // access timeline: this lane's own add (the callers' lanes are diverged; no merge here)
+    const uint64_t pad = p.entries[e].pad1;
+    timeline_add(p, pad != kTlNone, timeline_cell(p, pad, ts, th, page), 0);
   }
 }
 
@@ -536,7 +542,7 @@ struct XF {
   bool routed;
 };
 
-template <bool TIMING>
+template <bool TIMING, bool TL>
 __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
   __shared__ uint64_t s_pb[kMaxParts + 1];
   __shared__ uint16_t s_pdir[kRouteDir];
@@ -931,7 +937,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
           } else {  // attributed at once
             XRec xr = x_decode(rp.xl, pbq, X.a);
             if (xr.esc) x_resolve(xr, rp.xl, p.data, p.sbufs);
-            direct_attribute(p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, X.lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
+            direct_attribute<TL>(p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, X.lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
                              xr.g(rp.xl));
           }
         }
@@ -1005,7 +1011,7 @@ __global__ __launch_bounds__(256) void overflow_kernel(RouteParams rp) {
     const uint32_t lvl = (rp.p.flags & NMG_F_OBJECT_LEVELS)
                              ? raw_mem_lvl(rp.p.data, rp.p.sbufs[xr.g(rp.xl)].offset + xr.off(rp.xl))
                              : 0u;
-    direct_attribute(rp.p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
+    direct_attribute<true>(rp.p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
                      xr.g(rp.xl));
   }
 }
@@ -1199,7 +1205,7 @@ __device__ __forceinline__ int32_t match_older_pos(const Params& p, uint32_t fir
 
 // PACKED: an online table with packed page cells (LocalParams::pe_cmap; a
 // variant of its own, so that the offline table's flush carries none of it).
-// EXTRA: the outputs of NMG_F_OBJECT_LEVELS and NMG_F_SAMPLE_MATCHES (the
+// EXTRA: the outputs of NMG_F_OBJECT_LEVELS, NMG_F_SAMPLE_MATCHES and the access timeline (the
 // extras block at the end of `process`; again a variant of its own: the
 // instances without it are the code they were before it existed)
 template <bool TIMING, bool PACKED, bool EXTRA>
@@ -1639,10 +1645,11 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         // attribute_kernel; the id is the entry id, so an online table's map
         // applies.
         const bool lev = (p.flags & NMG_F_OBJECT_LEVELS) != 0;
+        const bool tlon = p.tl != nullptr;  // access timeline set: the matched records' cells
         bool need[kLC], any = false;
 #pragma unroll
         for (int j = 0; j < kLC; j++) {
-          need[j] = valid[j] && (p.smatch != nullptr || (lev && erel[j] >= 0));
+          need[j] = valid[j] && (p.smatch != nullptr || ((lev || tlon) && erel[j] >= 0));
           any |= need[j];
         }
         if (__ballot(any)) {
@@ -1691,6 +1698,22 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
                 todo &= ~sm;
               }
               if (row[j] && !small) level_count(p, eid[j], xr[j].acc, lvl[j], w[j]);
+            }
+          }
+          // The timeline cells (wave-uniform here: behind the ballot above).
+          // The entry's base is one gather of its by-id record, all kLC in
+          // flight before the first merge; the timestamp is the compact
+          // record's (escaped: the re-read absolute one).
+          if (tlon) {
+            uint64_t pad[kLC];
+#pragma unroll
+            for (int j = 0; j < kLC; j++)
+              pad[j] = need[j] && erel[j] >= 0 ? p.entries[eid[j]].pad1 : kTlNone;
+#pragma unroll
+            for (int j = 0; j < kLC; j++) {
+              const uint64_t ft = xr[j].esc ? ts[j] : lp.xl.tbase + ts[j];
+              timeline_add(p, pad[j] != kTlNone,
+                           timeline_cell(p, pad[j], ft, xr[j].th, uint32_t(int(pofs[j] / kPageSize))), p.tl_rounds);
             }
           }
           vm_drain();
@@ -1871,8 +1894,13 @@ __global__ __launch_bounds__(kWG) void found_kernel(FoundParams r) {
 // launchers
 
 hipError_t launch_route(uint32_t grid, hipStream_t s, const RouteParams& r) {
-  if (r.p.flags & kDbgRouteTiming) hipLaunchKernelGGL(route2_kernel<true>, dim3(grid), dim3(kR2WG), 0, s, r);
-  else hipLaunchKernelGGL(route2_kernel<false>, dim3(grid), dim3(kR2WG), 0, s, r);
+  // (TL: an instance of its own for engines with a timeline set, so that the
+  // other one is the code it was before the timeline existed)
+  const bool timing = (r.p.flags & kDbgRouteTiming) != 0, tl = r.p.tl != nullptr;
+  if (timing && tl) hipLaunchKernelGGL((route2_kernel<true, true>), dim3(grid), dim3(kR2WG), 0, s, r);
+  else if (timing) hipLaunchKernelGGL((route2_kernel<true, false>), dim3(grid), dim3(kR2WG), 0, s, r);
+  else if (tl) hipLaunchKernelGGL((route2_kernel<false, true>), dim3(grid), dim3(kR2WG), 0, s, r);
+  else hipLaunchKernelGGL((route2_kernel<false, false>), dim3(grid), dim3(kR2WG), 0, s, r);
   return hipGetLastError();
 }
 
@@ -1906,7 +1934,7 @@ static void launch_local_as(bool extra, uint32_t grid, hipStream_t s, const Loca
 // the extras variant for engines with per-object levels or per-sample matches
 hipError_t launch_local(uint32_t grid, hipStream_t s, const LocalParams& r) {
   const bool timing = (r.p.flags & kDbgLocalTiming) != 0, packed = r.pe_cmap != nullptr;
-  const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr;
+  const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr || r.p.tl != nullptr;
   if (packed) {
     if (timing) launch_local_as<true, true>(extra, grid, s, r);
     else launch_local_as<false, true>(extra, grid, s, r);

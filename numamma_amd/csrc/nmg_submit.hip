@@ -640,6 +640,14 @@ Params base_params(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, co
   p.sparse_vals = h->cnt.d_sparse_vals;
   p.sparse_dirty = h->cnt.d_sparse_dirty ? h->cnt.d_sparse_dirty + (h->nreset & 1) : nullptr;
   p.smatch = (h->flags & NMG_F_SAMPLE_MATCHES) ? h->d_smatch : nullptr;
+  if (h->tl.on) {
+    p.tl = h->tl.d_cells;
+    p.tl_t0 = h->tl.opt.t0;
+    p.tl_bin_shift = h->tl.opt.bin_shift;
+    p.tl_nb_bins = h->tl.opt.nb_bins;
+    p.tl_row_shift = h->tl.opt.row_shift;
+    p.tl_rounds = h->tl.rounds;
+  }
   return p;
 }
 

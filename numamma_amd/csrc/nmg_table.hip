@@ -427,6 +427,7 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   free_table(h);  // (released before the new ones are allocated: no second table's worth of HBM)
   h->cnt = Counters();
+  h->tl = Timeline();  // (a timeline is laid out for one table)
   h->lk.K = nb_keys;
   h->E = nb_entries;
 
@@ -479,6 +480,76 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
   return nmg_reset_counters(h);
 }
 
+
+// The access timeline's cells for the current table: every entry with dense
+// page cells (CellCursor::place) and at least min_object_bytes gets
+// nb_bins * T * R cells, in id order; its base and R go into pad1 of its
+// by-id record (tl_pad; kTlNone for the others), which is what the kernels
+// gather.  The table-order copies of an nmg_update_objects table (chain, node
+// records) carry pad1 too but nothing reads it there, so a later accepted
+// update -- it rebuilds those from the host records -- keeps the bases.
+extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
+  if (!h) return NMG_ERR_INVALID;
+  h->epoch++;
+  if (h->multi || !h->workers.empty()) return fail(h, NMG_ERR_INVALID, "nmg_set_timeline: not on a multi-GPU handle");
+  constexpr uint32_t kNeed = NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST;
+  if ((h->flags & kNeed) != kNeed)
+    return fail(h, NMG_ERR_INVALID, "nmg_set_timeline needs an engine created with NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST");
+  if (o && (o->bin_shift > 63 || o->nb_bins < 1 || o->nb_bins > 4096 || o->row_shift > 20 || o->reserved != 0))
+    return fail(h, NMG_ERR_INVALID, "nmg_set_timeline: option out of range (bin_shift <= 63, nb_bins 1..4096, "
+                                    "row_shift <= 20, reserved 0)");
+  if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_set_timeline before nmg_set_objects");
+  if (h->streaming) return fail(h, NMG_ERR_STATE, "nmg_set_timeline while a stream is open");
+  HIP_TRY(h, hipSetDevice(h->device));
+  int rc = route_settle(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // launches in flight read the entries and the cells
+  if (!o) {
+    h->tl = Timeline();
+    return NMG_OK;
+  }
+  EntryTable& tab = h->tab;
+  const uint32_t E = h->E, T = h->T;
+  Timeline t;
+  t.opt = *o;
+  if (const char* r = getenv("NMG_TL_ROUNDS")) t.rounds = (uint32_t)std::min(64, std::max(0, atoi(r)));  // (see kTlRounds)
+  const uint64_t budget = o->budget_bytes ? o->budget_bytes : (1ull << 30);
+  unsigned __int128 need = 0;
+  for (uint32_t e = 0; e < E; e++) {
+    if (tab.hist_base[e] == kHistSparse || tab.buffer_size[e] < o->min_object_bytes) continue;
+    const uint64_t R = (tab.buffer_size[e] / kPageSize + 1 + (1ull << o->row_shift) - 1) >> o->row_shift;
+    if (need <= 0xffffffffull) {  // (past it the layout is refused below: only the size is still summed)
+      t.ids.push_back(e);
+      t.base.push_back((uint32_t)need);
+      t.nrows.push_back((uint32_t)R);  // (dense: R <= pages <= kMaxEntryCells)
+    }
+    need += (unsigned __int128)R * o->nb_bins * T;
+  }
+  const unsigned __int128 bytes = need * 4;
+  if (need > 0xffffffffull || bytes > budget) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "nmg_set_timeline: the cells need %llu bytes (budget %llu, at most 2^32 - 1 cells)",
+             bytes > ~0ull ? ~0ull : (unsigned long long)bytes, (unsigned long long)budget);
+    return fail(h, NMG_ERR_CAPACITY, msg);
+  }
+  t.ncells = (uint64_t)need;
+  t.base.push_back((uint32_t)t.ncells);
+  // the new layout beside the current one; committed once everything is uploaded
+  std::vector<DevEntry> dev = tab.dev_entries;
+  for (DevEntry& d : dev) d.pad1 = kTlNone;
+  for (size_t k = 0; k < t.ids.size(); k++) dev[t.ids[k]].pad1 = tl_pad(t.base[k], t.nrows[k]);
+  HIP_TRY(h, t.d_cells.alloc(t.ncells));
+  HIP_TRY(h, hipMemsetAsync(t.d_cells, 0, t.ncells * 4, h->stream));
+  HIP_TRY(h, alloc_copy(h, t.d_ids, t.ids));
+  HIP_TRY(h, alloc_copy(h, t.d_base, t.base));
+  HIP_TRY(h, alloc_copy(h, t.d_nrows, t.nrows));
+  if (E) HIP_TRY(h, hipMemcpyAsync(h->d_entries, dev.data(), (size_t)E * sizeof(DevEntry), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (pageable sources)
+  tab.dev_entries = std::move(dev);
+  t.on = true;
+  h->tl = std::move(t);
+  return NMG_OK;
+}
 
 // A live --online-analysis table (nmg_update_objects) may hold entries the
 // engine has not seen: objects created since the previous alarm (ids E ..
@@ -622,6 +693,12 @@ extern "C" int nmg_update_objects(nmg_engine* h, const uint64_t* keys, const uin
   const uint32_t n = nb_keys ? entry_off[nb_keys] : 0;
   int rc = check_table(h, keys, nb_keys ? entry_off : nullptr, nb_keys, n);
   if (rc) return rc;
+  // with a timeline set, its layout stands: no new entry, no size other than the one it was laid out for
+  if (h->tl.on)
+    for (uint32_t j = 0; j < n; j++)
+      if (entry_ids[j] >= h->E || objects[j].buffer_size != h->tab.buffer_size[entry_ids[j]])
+        return fail(h, NMG_ERR_STATE, "nmg_update_objects: with a timeline set, a table may only list existing "
+                                      "entries with their sizes unchanged (drop it with nmg_set_timeline(h, NULL))");
   // ids: each at most once; new ones (>= E) consecutive from E
   uint32_t newE = h->E;
   for (uint32_t j = 0; j < n; j++) newE = std::max(newE, entry_ids[j] + 1);

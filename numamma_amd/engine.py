@@ -305,6 +305,34 @@ class Engine:
         self._c(lib.nmg_report(self.h, meta, C.byref(ro), stdout_path.encode() if stdout_path else None))
         del keep
 
+    # ---- access timeline
+    def set_timeline(self, t0: Optional[int] = 0, bin_shift: int = 0, nb_bins: int = 1, row_shift: int = 0,
+                     min_object_bytes: int = 0, budget_bytes: int = 0, reserved: int = 0):
+        """nmg_set_timeline: u32 counters [time bin][thread][row] per selected
+        object, counted by every analysis from now on.  set_timeline(None)
+        drops the timeline."""
+        if t0 is None:
+            self._c(lib.nmg_set_timeline(self.h, None))
+            return
+        o = _lib.nmg_timeline_options(t0, bin_shift, nb_bins, row_shift, reserved, min_object_bytes, budget_bytes)
+        self._c(lib.nmg_set_timeline(self.h, C.byref(o)))
+
+    def timeline_cells(self) -> np.ndarray:
+        """The non-zero timeline cells as (entry, bin, thread, row, count) rows,
+        sorted by (entry, bin, thread, row)."""
+        n = lib.nmg_count_timeline_cells(self.h)
+        self._c(n)
+        rows = np.empty((n, 5), dtype=np.uint32)  # (every row written by the engine)
+        self._c(lib.nmg_get_timeline_cells(self.h, _ptr(rows, C.c_uint32), n))
+        return rows
+
+    def report_timeline(self, output_dir: str, online: bool = False):
+        """nmg_report_timeline: callsite_timeline_<id>.dat per call site."""
+        meta, keep = build_meta(self.table)
+        ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
+        self._c(lib.nmg_report_timeline(self.h, meta, C.byref(ro)))
+        del keep
+
     # ---- multi-GPU merge helpers
     def array_size(self, which: int) -> int:
         return int(lib.nmg_array_size(self.h, which))

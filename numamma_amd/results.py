@@ -103,7 +103,43 @@ def report_host(res: RawResults, table, buf_bytes: np.ndarray, output_dir: str,
     dump_flags: NMG_DUMP_ALL writes all_memory_objects.dat (the sample dumps
     need the engine's per-sample matches: nmg_report)."""
     from . import _lib
-    from .engine import build_meta, table_objects
+    from .engine import build_meta
+
+    hr, keep = _host_results(res, table, buf_bytes, match_samples)
+    meta, kmeta = build_meta(table)
+    marr, nmods = _lib.module_array(modules)
+    ro = _lib.nmg_report_options(output_dir.encode(), dump_single_items, dump_flags, None, None, marr, nmods,
+                                 int(online))
+    _lib.check(_lib.lib.nmg_report_host(C.byref(hr), meta, C.byref(ro),
+                                        stdout_path.encode() if stdout_path else None))
+    del keep, kmeta
+
+
+def report_timeline_host(res: RawResults, table, output_dir: str, rows: np.ndarray, online: bool = False,
+                         **timeline) -> None:
+    """nmg_report_timeline_host(): callsite_timeline_<id>.dat files from host
+    arrays (no GPU involved).  rows: (entry, bin, thread, row, count) as
+    Engine.timeline_cells() returns them; timeline: the nmg_timeline_options
+    fields the rows were counted with (t0, bin_shift, nb_bins, row_shift, ...)."""
+    from . import _lib
+    from .engine import build_meta
+
+    hr, keep = _host_results(res, table, np.zeros(res.nb_buffers, dtype=np.uint64), True)
+    meta, kmeta = build_meta(table)
+    ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
+    tl = _lib.nmg_timeline_options(timeline.get("t0", 0), timeline.get("bin_shift", 0), timeline.get("nb_bins", 1),
+                                   timeline.get("row_shift", 0), timeline.get("reserved", 0),
+                                   timeline.get("min_object_bytes", 0), timeline.get("budget_bytes", 0))
+    rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 5)
+    _lib.check(_lib.lib.nmg_report_timeline_host(C.byref(hr), meta, C.byref(ro), C.byref(tl),
+                                                 rows.ctypes.data_as(C.POINTER(C.c_uint32)), rows.shape[0]))
+    del keep, kmeta
+
+
+def _host_results(res: RawResults, table, buf_bytes: np.ndarray, match_samples: bool):
+    """struct nmg_host_results over res's arrays, and what keeps them alive."""
+    from . import _lib
+    from .engine import table_objects
 
     hr = _lib.nmg_host_results()
     gbytes = np.ascontiguousarray(res.global_counters, dtype="<u8").tobytes()
@@ -130,10 +166,4 @@ def report_host(res: RawResults, table, buf_bytes: np.ndarray, output_dir: str,
     objs = table_objects(table)
     keep.append(objs)
     hr.objects = objs.ctypes.data_as(C.POINTER(_lib.nmg_object))
-    meta, kmeta = build_meta(table)
-    marr, nmods = _lib.module_array(modules)
-    ro = _lib.nmg_report_options(output_dir.encode(), dump_single_items, dump_flags, None, None, marr, nmods,
-                                 int(online))
-    _lib.check(_lib.lib.nmg_report_host(C.byref(hr), meta, C.byref(ro),
-                                        stdout_path.encode() if stdout_path else None))
-    del keep, kmeta
+    return hr, keep
