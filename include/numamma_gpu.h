@@ -499,8 +499,90 @@ int nmg_report_timeline_host(const struct nmg_host_results *res, const struct nm
                              const struct nmg_timeline_options *tl,
                              const uint32_t *rows, int64_t n);
 
+/* ---- NUMA placement: which node each page of an object, or of a call site,
+ * should live on, as blocks the reference's libnuma_run.so binds
+ * (NUMAMMA_MBIND_POLICY=custom NUMAMMA_MBIND_FILE=<output_dir>/blocks.dat,
+ * src/mem_run.c:524-581, 816-863).  The rule of scripts/counters_to_binding.py
+ * over the page histogram, computed on the device: the page cells stay there.
+ * nmg_get_object_blocks copies out the block rows alone; nmg_report_placement
+ * also downloads what the call-site registry needs (first-match ordinal, counts
+ * and weights: 5 words per entry), as nmg_report does.
+ *
+ * A group is one object (nmg_*_object_blocks; group = entry id, R = its
+ * pages) or one call site (nmg_report_placement; group = site id, members =
+ * the site's objects, R = the rows of its callsite_counters_<id>.dat, a
+ * member's pages past R dropped).  Only entries with dense page cells
+ * contribute (huge ranges such as [stack] do not: the timeline's selection).
+ * For page p < R and node n:
+ *   c[p][n] = sum over the members e with p < pages(e) and the threads t with
+ *             thread_node[t] == n of the page cell (e, t, p)      (u64 sums)
+ *   dom(p)  = the smallest n with the largest c[p][n], cnt(p) = c[p][dom(p)]
+ *   p qualifies iff cnt(p) > density_threshold.
+ * Walking p upward, a qualifying page whose dom differs from the previous
+ * qualifying page's (or the first one) opens a block {node, start = end = p,
+ * count = cnt(p)}; one with the same dom extends the open block (end = p,
+ * count += cnt(p)); a page that does not qualify changes nothing, so a block
+ * may span such pages.  A row is (group, node, start_page, end_page, count),
+ * rows sorted by (group, start_page).
+ *
+ * Deliberate differences from the script:
+ *   - page numbers: every page advances the page number (the script's
+ *     cur_block advances on qualifying pages only, so its start_page /
+ *     end_page are not page numbers);
+ *   - thread map: explicit; thread_node == NULL is the script's
+ *     rank / (nb_threads / nb_nodes), accepted only when nb_nodes divides
+ *     nb_threads (the script's integer division leaves threads without a
+ *     node otherwise);
+ *   - block count: a group with a single block is emitted (the script's
+ *     `if nblocks > 0` tests the count minus one and drops it);
+ *   - identifier: what load_custom_block / bind_malloced_buffer match on
+ *     (below), not the summary's name column.
+ *
+ * blocks.dat, for every site with at least one block in ascending site id:
+ *   #site <id> <caller string>
+ *   begin_block
+ *   <identifier> <site size> <nblocks>
+ *   <node> <start_page> <end_page> <count>        (one line per block)
+ *   end_block
+ * (load_custom_mbind skips lines outside a block.)  <site size> is the
+ * creating object's initial_buffer_size: what malloc was asked for, and what
+ * bind_malloced_buffer compares.  <identifier> is "malloc" for
+ * dynamic_allocation sites (mem_run.c:532) and the caller string -- the
+ * symbol -- for global_symbol sites.  Sites of type stack, lib or none are
+ * skipped, and so are sites whose identifier would be empty or holds
+ * whitespace, '[' or '/' (scripts/create_blocks.in's filter).
+ *
+ * Errors: NMG_ERR_INVALID for a NULL argument, nb_nodes outside 1..64, a
+ * thread_node value >= nb_nodes, a NULL thread_node with nb_threads not a
+ * multiple of nb_nodes, reserved != 0, or an engine without
+ * NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST; NMG_ERR_STATE before
+ * nmg_set_objects; NMG_ERR_IO when blocks.dat cannot be written.  Multi-GPU
+ * handles, streamed and online engines are accepted: the rule reads the
+ * (merged) histogram only.  The object blocks are cached per results epoch
+ * and options: nmg_count_object_blocks then nmg_get_object_blocks computes
+ * once.  nmg_report_placement gives its sites the ids nmg_report gives them
+ * (opts->online as there); nmg_report_placement_host computes the same file
+ * from res->cells with no GPU (rank 0 of the one-process-per-GPU chain),
+ * taking an entry's cells as dense when pages * nb_threads <= 2^24, the
+ * engine's per-entry cap. */
+struct nmg_placement_options {
+  uint32_t nb_nodes;            /* 1..64 */
+  uint32_t density_threshold;   /* a page qualifies when its dominant node's count > this; the script's value is 8 */
+  const uint32_t *thread_node;  /* [nb_threads], each < nb_nodes; NULL: rank / (nb_threads / nb_nodes),
+                                   nb_threads % nb_nodes == 0 */
+  uint64_t reserved;            /* 0 */
+};
+int64_t nmg_count_object_blocks(nmg_engine *h, const struct nmg_placement_options *p);
+int nmg_get_object_blocks(nmg_engine *h, const struct nmg_placement_options *p, uint64_t *rows /* [n][5] */, int64_t n);
+int nmg_report_placement(nmg_engine *h, const struct nmg_object_meta *meta, const struct nmg_report_options *opts,
+                         const struct nmg_placement_options *p);
+int nmg_report_placement_host(const struct nmg_host_results *res, const struct nmg_object_meta *meta,
+                              const struct nmg_report_options *opts, const struct nmg_placement_options *p);
+
 /* Convenience driver used by the nmg_replay CLI and the tests: load a replay
- * file (DESIGN.md "Replay format"), analyse it on `device`, report. */
+ * file (DESIGN.md "Replay format"), analyse it on `device`, report.
+ * Environment: NMG_REPLAY_PLACEMENT=nb_nodes[:threshold] also writes
+ * blocks.dat (nmg_report_placement, the NULL thread map, threshold 8). */
 int nmg_run_replay(const char *replay_path, const char *output_dir, const char *stdout_path,
                    const char *raw_path, int device, uint32_t flags);
 

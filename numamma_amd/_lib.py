@@ -148,6 +148,24 @@ class nmg_timeline_options(C.Structure):
                 ("reserved", C.c_uint32), ("min_object_bytes", C.c_uint64), ("budget_bytes", C.c_uint64)]
 
 
+class nmg_placement_options(C.Structure):
+    _fields_ = [("nb_nodes", C.c_uint32), ("density_threshold", C.c_uint32), ("thread_node", C.POINTER(C.c_uint32)),
+                ("reserved", C.c_uint64)]
+
+
+def placement_options(nb_threads, nb_nodes, thread_node=None, density_threshold=8, reserved=0):
+    """(nmg_placement_options, the array it points into): thread_node None is
+    the NULL map, rank / (nb_threads / nb_nodes); otherwise one node per thread
+    rank (the library reads nb_threads entries)."""
+    import numpy as np
+
+    tn = None if thread_node is None else np.ascontiguousarray(thread_node, dtype=np.uint32).reshape(-1)
+    if tn is not None and tn.shape[0] != nb_threads:
+        raise ValueError(f"thread_node has {tn.shape[0]} entries for {nb_threads} threads")
+    ptr = tn.ctypes.data_as(C.POINTER(C.c_uint32)) if tn is not None else None
+    return nmg_placement_options(nb_nodes, density_threshold, ptr, reserved), tn
+
+
 class nmg_results_view(C.Structure):
     _fields_ = [
         ("global_", nmg_mem_counters * 2),
@@ -212,6 +230,14 @@ _SIGS = {
     "nmg_report_timeline_host": (C.c_int, [C.POINTER(nmg_host_results), C.POINTER(nmg_object_meta),
                                            C.POINTER(nmg_report_options), C.POINTER(nmg_timeline_options), u32p,
                                            C.c_int64]),
+    "nmg_count_object_blocks": (C.c_int64, [H, C.POINTER(nmg_placement_options)]),
+    "nmg_get_object_blocks": (C.c_int, [H, C.POINTER(nmg_placement_options), u64p, C.c_int64]),
+    "nmg_report_placement": (C.c_int, [H, C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options),
+                                       C.POINTER(nmg_placement_options)]),
+    "nmg_report_placement_host": (C.c_int, [C.POINTER(nmg_host_results), C.POINTER(nmg_object_meta),
+                                            C.POINTER(nmg_report_options), C.POINTER(nmg_placement_options)]),
+    "nmg_debug_object_blocks_host": (C.c_int64, [C.POINTER(nmg_host_results), C.POINTER(nmg_placement_options), u64p,
+                                                 C.c_int64]),
     "nmg_results_begin": (C.c_int, [H]),
     "nmg_results_end": (C.c_int, [H, C.POINTER(nmg_results_view)]),
     "nmg_array_size": (C.c_uint64, [H, C.c_int]),

@@ -413,6 +413,35 @@ extern "C" uint32_t nmg_get_nb_buffers(nmg_engine* h) {
   return h->counts_override ? (uint32_t)h->ov_samples.size() : (uint32_t)h->descs.size();
 }
 
+// What the call-site registry reads per entry (buffer_size, first_ordinal,
+// count_weight), set in res in the report's walk order: the id order, or, for
+// live online tables, the order of the latest table that listed every entry
+// (h->order; meta follows it), with w.pos the walk position of each id.
+int walk_counters(nmg_engine* h, const HostResults& r, nmg_host_results& res, WalkCounters& w) {
+  const uint32_t E = h->E;
+  res.nb_entries = E;
+  res.buffer_size = h->tab.buffer_size.data();
+  res.first_ordinal = r.first.data();
+  res.count_weight = r.count_weight.data();
+  if (h->order.empty()) return NMG_OK;
+  if (h->order.size() != E) return fail(h, NMG_ERR_STATE, "report walk order does not cover every entry");
+  w.pos.resize(E);
+  w.size.resize(E);
+  w.first.resize(E);
+  w.cw.resize((size_t)E * 4);
+  for (uint32_t k = 0; k < E; k++) {
+    const uint32_t id = h->order[k];
+    w.pos[id] = k;
+    w.size[k] = h->tab.buffer_size[id];
+    w.first[k] = r.first[id];
+    for (int q = 0; q < 4; q++) w.cw[(size_t)k * 4 + q] = r.count_weight[(size_t)id * 4 + q];
+  }
+  res.buffer_size = w.size.data();
+  res.first_ordinal = w.first.data();
+  res.count_weight = w.cw.data();
+  return NMG_OK;
+}
+
 extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_report_options* opts,
                           const char* stdout_path) {
   Range range("nmg_report");
@@ -439,13 +468,9 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   res.global[0] = r.global[0];
   res.global[1] = r.global[1];
   res.nb_buffers = (uint32_t)r.buf_samples.size();
-  res.nb_entries = h->E;
   res.buf_samples = r.buf_samples.data();
   res.buf_found = r.buf_found.data();
   res.buf_bytes = r.buf_bytes.data();
-  res.buffer_size = h->tab.buffer_size.data();
-  res.first_ordinal = r.first.data();
-  res.count_weight = r.count_weight.data();
   res.cells = rows.data();
   res.nb_cells = ncells;
   res.nb_threads = h->T;
@@ -453,26 +478,18 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   res.objects = h->tab.objects.data();
   // live online tables: entries walked in the order of the latest table that
   // listed them all (ids are creation order there); meta follows that order
-  std::vector<uint64_t> w_size, w_first, w_cw;
+  WalkCounters w;
   std::vector<nmg_object> w_obj;
   std::vector<uint32_t> w_rows;
+  if (!h->order.empty() && opts && opts->dump_flags)
+    return fail(h, NMG_ERR_STATE, "dump modes need the entries in id order");
+  rc = walk_counters(h, r, res, w);
+  if (rc) return rc;
   if (!h->order.empty()) {
-    if (opts && opts->dump_flags) return fail(h, NMG_ERR_STATE, "dump modes need the entries in id order");
     const uint32_t E = h->E;
-    if (h->order.size() != E) return fail(h, NMG_ERR_STATE, "report walk order does not cover every entry");
-    std::vector<uint32_t> pos(E);
-    w_size.resize(E);
-    w_first.resize(E);
-    w_cw.resize((size_t)E * 4);
+    const std::vector<uint32_t>& pos = w.pos;
     w_obj.resize(E);
-    for (uint32_t k = 0; k < E; k++) {
-      const uint32_t id = h->order[k];
-      pos[id] = k;
-      w_size[k] = h->tab.buffer_size[id];
-      w_first[k] = r.first[id];
-      for (int q = 0; q < 4; q++) w_cw[(size_t)k * 4 + q] = r.count_weight[(size_t)id * 4 + q];
-      w_obj[k] = h->tab.objects[id];
-    }
+    for (uint32_t k = 0; k < E; k++) w_obj[k] = h->tab.objects[h->order[k]];
     // page rows (entry, thread, page, count), grouped by walk position
     std::vector<uint32_t> idx((size_t)ncells);
     for (uint32_t i = 0; i < (uint32_t)ncells; i++) idx[i] = i;
@@ -485,9 +502,6 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
       w_rows[4 * i + 2] = q[2];
       w_rows[4 * i + 3] = q[3];
     }
-    res.buffer_size = w_size.data();
-    res.first_ordinal = w_first.data();
-    res.count_weight = w_cw.data();
     res.cells = w_rows.data();
     res.objects = w_obj.data();
   }
@@ -541,32 +555,12 @@ extern "C" int nmg_report_timeline(nmg_engine* h, const nmg_object_meta* meta, c
   if (rc) return rc;
   nmg_host_results res;
   memset(&res, 0, sizeof(res));
-  res.nb_entries = h->E;
-  res.buffer_size = h->tab.buffer_size.data();
-  res.first_ordinal = r.first.data();
-  res.count_weight = r.count_weight.data();
   res.nb_threads = h->T;
   res.match_samples = 1;
-  std::vector<uint64_t> w_size, w_first, w_cw;
-  if (!h->order.empty()) {  // (live online tables: meta follows the walk order)
-    const uint32_t E = h->E;
-    if (h->order.size() != E) return fail(h, NMG_ERR_STATE, "report walk order does not cover every entry");
-    std::vector<uint32_t> pos(E);
-    w_size.resize(E);
-    w_first.resize(E);
-    w_cw.resize((size_t)E * 4);
-    for (uint32_t k = 0; k < E; k++) {
-      const uint32_t id = h->order[k];
-      pos[id] = k;
-      w_size[k] = h->tab.buffer_size[id];
-      w_first[k] = r.first[id];
-      for (int q = 0; q < 4; q++) w_cw[(size_t)k * 4 + q] = r.count_weight[(size_t)id * 4 + q];
-    }
-    for (int64_t i = 0; i < n; i++) rows[5 * i] = pos[rows[5 * i]];  // (the writer groups by site: any order)
-    res.buffer_size = w_size.data();
-    res.first_ordinal = w_first.data();
-    res.count_weight = w_cw.data();
-  }
+  WalkCounters w;
+  rc = walk_counters(h, r, res, w);
+  if (rc) return rc;
+  for (int64_t i = 0; i < n && !w.pos.empty(); i++) rows[5 * i] = w.pos[rows[5 * i]];  // (the writer groups by site: any order)
   std::string err;
   rc = write_timeline(&res, meta, opts, &h->tl.opt, rows.data(), n, err);
   if (rc && !err.empty()) h->last_error = err;

@@ -265,6 +265,29 @@ struct Timeline {
   int64_t n = 0;
 };
 
+// NUMA placement (nmg_placement.hip): groups on the device (PlaceParams'
+// arrays), and the engine's state -- the object groups of the current table,
+// the kernels' work arrays and the object blocks of the current results epoch.
+struct PlaceDev {
+  uint32_t G = 0;
+  uint64_t pages = 0;
+  DevBuf<uint32_t> gid, m_off, m_np;
+  DevBuf<uint64_t> pg_off, m_base;
+};
+struct PlaceState {
+  bool obj_dirty = true;  // hist_base / npages changed: the object groups are built and uploaded again
+  PlaceDev obj;
+  DevBuf<uint32_t> d_thr, d_noff, d_bcnt;
+  DevBuf<uint64_t> d_pvcnt, d_boff, d_part;
+  DevBuf<uint8_t> d_pvnode;
+  // nmg_count_object_blocks, then the copy out: rows of this epoch and these options
+  DevBuf<uint64_t> d_rows;
+  uint64_t rows_epoch = 0;
+  uint32_t N = 0, D = 0;
+  std::vector<uint32_t> node;  // the thread -> node map of those rows (PlaceMap::node)
+  int64_t n = 0;
+};
+
 struct nmg_engine {
   int device = 0;
   uint32_t flags = NMG_F_DEFAULT;
@@ -342,6 +365,7 @@ struct nmg_engine {
   DevBuf<uint64_t> d_scratch;          // [2] small device results (nmg_hist_pack / unpack) + range counts
   DevBuf<uint32_t> d_smatch;           // NMG_F_SAMPLE_MATCHES: per 8 B of the arena span
   Timeline tl;                         // nmg_set_timeline (dropped with the table)
+  PlaceState place;                    // nmg_count_object_blocks / nmg_report_placement
   uint64_t nreset = 0;
 
   // buffers
@@ -525,6 +549,11 @@ int decode_error_word(nmg_engine* h, uint64_t w);
 int cells_prepare(nmg_engine* h);
 int cells_fill(nmg_engine* h, uint32_t* rows);
 int collect_page_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);
+struct WalkCounters {  // walk_counters' arrays (empty while the walk order is the id order)
+  std::vector<uint64_t> size, first, cw;
+  std::vector<uint32_t> pos;
+};
+int walk_counters(nmg_engine* h, const HostResults& r, nmg_host_results& res, WalkCounters& w);
 int timeline_prepare(nmg_engine* h);
 int collect_timeline_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);  // [n][5]
 void* array_ptr(nmg_engine* h, int which, size_t* bytes);

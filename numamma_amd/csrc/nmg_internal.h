@@ -161,4 +161,42 @@ int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const n
 int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
                    const nmg_timeline_options* tl, const uint32_t* rows, int64_t n, std::string& err);
 
+// ---- NUMA placement (include/numamma_gpu.h): what the device path
+// (nmg_placement.hip), the host path and the writer (nmg_report.cpp) share.
+// The thread map as the fold reads it: thread ranks sorted by node, node n's
+// at thr[node_off[n] .. node_off[n + 1]).
+struct PlaceMap {
+  uint32_t N = 0, D = 0;
+  std::vector<uint32_t> thr, node_off;
+  std::vector<uint32_t> node;  // [T] the map itself: thread rank -> node
+};
+// p checked (NMG_ERR_INVALID) and laid out for T threads
+int placement_map(const nmg_placement_options* p, uint32_t T, PlaceMap& out);
+// Groups in ascending gid order, group g's members at [m_off[g], m_off[g + 1]).
+// rows[g] = min(R, the longest member): the pages past every member count
+// nothing and never qualify.  Groups without a dense member or a row are left out.
+struct PlaceGroups {
+  std::vector<uint32_t> gid, rows, m_off{0};
+  std::vector<uint32_t> m_entry, m_np;  // member: its entry (report position), pages clipped to R
+  void add(uint32_t id, uint64_t R, const std::vector<uint32_t>& entries, const uint64_t* npages,
+           const uint8_t* dense);
+};
+struct PlaceSite {  // a call site that may get blocks
+  uint32_t id;
+  std::string caller, ident;
+  uint64_t size;
+};
+// every entry with dense cells its own group
+void placement_object_groups(uint32_t E, const uint64_t* npages, const uint8_t* dense, PlaceGroups& g);
+// the call sites of r (nmg_report's ids) that blocks.dat may list, one group each
+int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta, bool online,
+                          const uint64_t* npages, const uint8_t* dense, PlaceGroups& g,
+                          std::vector<PlaceSite>& sites, std::string& err);
+// the rule on the host, from (entry, thread, page, count) cells sorted by entry: [n][5] rows appended
+void placement_blocks_host(const PlaceGroups& g, const PlaceMap& m, const uint32_t* cells, int64_t nb_cells,
+                           uint32_t nb_entries, std::vector<uint64_t>& rows);
+// blocks.dat from the sites (ascending id) and their rows (group = site id)
+int write_blocks(const std::vector<PlaceSite>& sites, const uint64_t* rows, int64_t n,
+                 const nmg_report_options* opts, std::string& err);
+
 }  // namespace nmg

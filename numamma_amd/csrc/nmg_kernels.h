@@ -270,4 +270,29 @@ hipError_t launch_tl_emit(hipStream_t s, const uint32_t* tl, uint64_t ncells, co
                           const uint32_t* base, const uint32_t* nrows, uint32_t n, uint32_t T, const uint64_t* off,
                           uint32_t* rows);
 
+// NUMA placement blocks on the device (nmg_placement.hip; the rule is in
+// include/numamma_gpu.h).  The groups' pages are numbered consecutively:
+// group g's page p is group page pg_off[g] + p, pg_off[G] of them in all.
+struct PlaceParams {
+  const uint32_t* hist;  // the page histogram: cell (t, c) at t * hist_cells + c
+  uint64_t hist_cells;
+  const uint32_t* thr;       // [T] thread ranks sorted by node
+  const uint32_t* node_off;  // [N + 1] node n's ranks at thr[node_off[n] .. node_off[n + 1])
+  uint32_t N, D, G;
+  const uint32_t* gid;      // [G] ascending
+  const uint64_t* pg_off;   // [G + 1] strictly ascending (every group has a row)
+  const uint32_t* m_off;    // [G + 1] group g's members [m_off[g], m_off[g + 1])
+  const uint64_t* m_base;   // [M] member's first cell
+  const uint32_t* m_np;     // [M] member's pages (<= the group's rows)
+  uint64_t* pv_cnt;         // [pages] cnt(p)
+  uint8_t* pv_node;         // [pages] dom(p) of a qualifying page, kPlaceNoNode otherwise
+  uint32_t* bcnt;           // [G] blocks per group
+  const uint64_t* boff;     // [G + 1] their exclusive scan
+  uint64_t* rows;           // [blocks][5], zeroed before the emit pass
+};
+constexpr uint32_t kPlaceNoNode = 0xff;
+hipError_t launch_place_fold(hipStream_t s, const PlaceParams& p, uint64_t pages);
+hipError_t launch_place_count(hipStream_t s, const PlaceParams& p);
+hipError_t launch_place_emit(hipStream_t s, const PlaceParams& p);
+
 }  // namespace nmg

@@ -364,6 +364,19 @@ extern "C" int nmg_run_replay(const char* replay_path, const char* output_dir, c
   ro.nb_modules = (uint32_t)r.modules.size();
   rc = nmg_report(h, r.meta.data(), &ro, stdout_path);
   if (rc) return bail(rc);
+  // NMG_REPLAY_PLACEMENT=nb_nodes[:threshold]: blocks.dat after the report
+  // (the NULL thread map; threshold 8 as scripts/counters_to_binding.py)
+  const char* place = getenv("NMG_REPLAY_PLACEMENT");
+  if (place && *place) {
+    unsigned nodes = 0, thr = 8;
+    sscanf(place, "%u:%u", &nodes, &thr);
+    nmg_placement_options po;
+    memset(&po, 0, sizeof(po));
+    po.nb_nodes = nodes;
+    po.density_threshold = thr;
+    rc = nmg_report_placement(h, r.meta.data(), &ro, &po);
+    if (rc) return bail(rc);
+  }
   if (raw_path) {
     rc = write_raw(h, r, raw_path);
     if (rc) return bail(rc);

@@ -515,6 +515,160 @@ int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const
   return NMG_OK;
 }
 
+// ---- NUMA placement (the rule, the file and their differences from
+// scripts/counters_to_binding.py are in include/numamma_gpu.h)
+
+int placement_map(const nmg_placement_options* p, uint32_t T, PlaceMap& out) {
+  if (!p || p->nb_nodes < 1 || p->nb_nodes > 64 || p->reserved) return NMG_ERR_INVALID;
+  const uint32_t N = p->nb_nodes;
+  if (!p->thread_node && T % N) return NMG_ERR_INVALID;
+  std::vector<uint32_t>& node = out.node;
+  node.assign(T, 0);
+  out.node_off.assign(N + 1, 0);
+  for (uint32_t t = 0; t < T; t++) {
+    node[t] = p->thread_node ? p->thread_node[t] : t / (T / N);
+    if (node[t] >= N) return NMG_ERR_INVALID;
+    out.node_off[node[t] + 1]++;
+  }
+  for (uint32_t n = 0; n < N; n++) out.node_off[n + 1] += out.node_off[n];
+  std::vector<uint32_t> at(out.node_off.begin(), out.node_off.end() - 1);
+  out.thr.resize(T);
+  for (uint32_t t = 0; t < T; t++) out.thr[at[node[t]]++] = t;
+  out.N = N;
+  out.D = p->density_threshold;
+  return NMG_OK;
+}
+
+void PlaceGroups::add(uint32_t id, uint64_t R, const std::vector<uint32_t>& entries, const uint64_t* npages,
+                      const uint8_t* dense) {
+  const size_t m0 = m_entry.size();
+  uint32_t longest = 0;
+  for (uint32_t e : entries) {
+    if (!dense[e]) continue;
+    const uint32_t np = (uint32_t)std::min<uint64_t>(npages[e], R);  // (dense: pages * threads <= 2^24)
+    if (!np) continue;
+    m_entry.push_back(e);
+    m_np.push_back(np);
+    longest = std::max(longest, np);
+  }
+  if (m_entry.size() == m0) return;
+  gid.push_back(id);
+  rows.push_back(longest);
+  m_off.push_back((uint32_t)m_entry.size());
+}
+
+void placement_object_groups(uint32_t E, const uint64_t* npages, const uint8_t* dense, PlaceGroups& g) {
+  std::vector<uint32_t> one(1);
+  for (uint32_t e = 0; e < E; e++) {
+    one[0] = e;
+    g.add(e, npages[e], one, npages, dense);
+  }
+}
+
+int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta, bool online,
+                          const uint64_t* npages, const uint8_t* dense, PlaceGroups& g,
+                          std::vector<PlaceSite>& sites, std::string& err) {
+  Registry reg(meta);
+  if (r->match_samples) {
+    const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
+    if (rc) return rc;
+  }
+  constexpr uint32_t kGlobalSymbol = 1, kDynamicAllocation = 3;  // enum mem_type, mem_analyzer.h:58-64
+  for (const Site& s : reg.sites) {  // (creation order: ascending id)
+    std::string ident;
+    if (s.mem_type == kDynamicAllocation) {
+      ident = "malloc";
+    } else if (s.mem_type == kGlobalSymbol) {
+      ident = s.caller;
+      if (ident.empty() || ident.find_first_of(" \t\n\v\f\r[/") != std::string::npos) continue;
+    } else {
+      continue;
+    }
+    const size_t g0 = g.gid.size();
+    g.add(s.id, s.mem_info_buffer_size / kPageSize + 1, s.objects, npages, dense);
+    if (g.gid.size() != g0) sites.push_back(PlaceSite{s.id, s.caller, ident, s.buffer_size});
+  }
+  return NMG_OK;
+}
+
+void placement_blocks_host(const PlaceGroups& g, const PlaceMap& m, const uint32_t* cells, int64_t nb_cells,
+                           uint32_t nb_entries, std::vector<uint64_t>& rows) {
+  const uint32_t T = (uint32_t)m.thr.size();
+  // the nodes that have a thread, in ascending order (the others count nothing
+  // and never win: a page's matrix row holds these only)
+  std::vector<uint32_t> used, col(T, 0);
+  for (uint32_t n = 0; n < m.N; n++)
+    if (m.node_off[n + 1] > m.node_off[n]) {
+      for (uint32_t k = m.node_off[n]; k < m.node_off[n + 1]; k++) col[m.thr[k]] = (uint32_t)used.size();
+      used.push_back(n);
+    }
+  const size_t U = used.size();
+  std::vector<int64_t> cell_begin((size_t)nb_entries + 1, 0);
+  for (int64_t i = 0; i < nb_cells; i++) cell_begin[cells[4 * i] + 1]++;
+  for (uint32_t e = 0; e < nb_entries; e++) cell_begin[e + 1] += cell_begin[e];
+  std::vector<uint64_t> c;
+  for (size_t gi = 0; gi < g.gid.size(); gi++) {
+    const uint32_t R = g.rows[gi];
+    c.assign((size_t)R * U, 0);
+    for (uint32_t k = g.m_off[gi]; k < g.m_off[gi + 1]; k++) {
+      const uint32_t e = g.m_entry[k], np = g.m_np[k];
+      for (int64_t i = cell_begin[e]; i < cell_begin[e + 1]; i++) {
+        const uint32_t* q = cells + 4 * i;
+        if (q[2] < np && q[1] < T) c[(size_t)q[2] * U + col[q[1]]] += q[3];
+      }
+    }
+    bool open = false;
+    uint32_t prev = 0;
+    for (uint32_t p = 0; p < R; p++) {
+      uint64_t best = 0;
+      uint32_t node = 0;
+      for (size_t u = 0; u < U; u++)
+        if (c[(size_t)p * U + u] > best) best = c[(size_t)p * U + u], node = used[u];  // (strict: the lowest node on a tie)
+      if (best <= m.D) continue;
+      if (!open || node != prev) {
+        const uint64_t row[5] = {g.gid[gi], node, p, p, best};
+        rows.insert(rows.end(), row, row + 5);
+        open = true;
+        prev = node;
+      } else {
+        rows[rows.size() - 2] = p;
+        rows[rows.size() - 1] += best;
+      }
+    }
+  }
+}
+
+int write_blocks(const std::vector<PlaceSite>& sites, const uint64_t* rows, int64_t n,
+                 const nmg_report_options* opts, std::string& err) {
+  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
+  mkdir(dir, S_IRWXU);
+  const std::string path = std::string(dir) + "/blocks.dat";
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) {
+    err = "cannot open " + path;
+    return NMG_ERR_IO;
+  }
+  int64_t i = 0;
+  for (const PlaceSite& s : sites) {  // (ascending id, as the rows' groups)
+    while (i < n && rows[5 * i] < s.id) i++;
+    int64_t j = i;
+    while (j < n && rows[5 * j] == s.id) j++;
+    if (j == i) continue;
+    fprintf(f, "#site %u %s\nbegin_block\n%s %" PRIu64 " %" PRId64 "\n", s.id, s.caller.c_str(), s.ident.c_str(),
+            s.size, j - i);
+    for (; i < j; i++)
+      fprintf(f, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", rows[5 * i + 1], rows[5 * i + 2],
+              rows[5 * i + 3], rows[5 * i + 4]);
+    fprintf(f, "end_block\n");
+  }
+  const bool bad = ferror(f) != 0;
+  if (fclose(f) != 0 || bad) {
+    err = "cannot write " + path;
+    return NMG_ERR_IO;
+  }
+  return NMG_OK;
+}
+
 int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
                  const char* stdout_path, std::string& err, const DumpInput* dump, const uint64_t* found_override) {
   // NMG_REPORT_TIMING=1: phase times on stderr
@@ -842,6 +996,66 @@ extern "C" int nmg_report_timeline_host(const nmg_host_results* res, const nmg_o
   int rc = nmg::write_timeline(res, meta, opts, tl, rows, n, err);
   if (rc && !err.empty()) fprintf(stderr, "nmg_report_timeline: %s\n", err.c_str());
   return rc;
+}
+
+namespace {
+// the host's view of the page cells: an entry's pages, and whether the engine
+// keeps them dense (CellCursor::place's per-entry cap; budgets aside)
+bool placement_host_args(const nmg_host_results* res, const nmg_placement_options* p, nmg::PlaceMap& map,
+                         std::vector<uint64_t>& npages, std::vector<uint8_t>& dense) {
+  if (!res || (res->nb_entries && !res->buffer_size) || (res->nb_cells && !res->cells) || res->nb_cells < 0 ||
+      res->nb_threads > NMG_MAX_THREADS || nmg::placement_map(p, res->nb_threads, map))
+    return false;
+  for (int64_t i = 0; i < res->nb_cells; i++)
+    if (res->cells[4 * i] >= res->nb_entries || (i && res->cells[4 * i] < res->cells[4 * i - 4])) return false;
+  npages.resize(res->nb_entries);
+  dense.resize(res->nb_entries);
+  for (uint32_t e = 0; e < res->nb_entries; e++) {
+    npages[e] = res->buffer_size[e] / nmg::kPageSize + 1;
+    dense[e] = npages[e] * std::max(1u, res->nb_threads) <= nmg::kMaxEntryCells;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int nmg_report_placement_host(const nmg_host_results* res, const nmg_object_meta* meta,
+                                         const nmg_report_options* opts, const nmg_placement_options* p) {
+  nmg::PlaceMap map;
+  std::vector<uint64_t> npages;
+  std::vector<uint8_t> dense;
+  if (!placement_host_args(res, p, map, npages, dense) ||
+      (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight)))
+    return NMG_ERR_INVALID;
+  std::string err;
+  nmg::PlaceGroups g;
+  std::vector<nmg::PlaceSite> sites;
+  std::vector<uint64_t> rows;
+  int rc = nmg::placement_site_groups(res, meta, opts && opts->online, npages.data(), dense.data(), g, sites, err);
+  if (!rc) {
+    nmg::placement_blocks_host(g, map, res->cells, res->nb_cells, res->nb_entries, rows);
+    rc = nmg::write_blocks(sites, rows.data(), (int64_t)(rows.size() / 5), opts, err);
+  }
+  if (rc && !err.empty()) fprintf(stderr, "nmg_report_placement: %s\n", err.c_str());
+  return rc;
+}
+
+// Internal (not in include/numamma_gpu.h; tools/placement_timing.py and the
+// tests): nmg_get_object_blocks' rows computed on the host from res->cells,
+// what a caller without the device path does after nmg_get_page_cells.
+// Returns the number of rows; the first min(n, cap) are written.
+extern "C" int64_t nmg_debug_object_blocks_host(const nmg_host_results* res, const nmg_placement_options* p,
+                                                uint64_t* rows, int64_t cap) {
+  nmg::PlaceMap map;
+  std::vector<uint64_t> npages;
+  std::vector<uint8_t> dense;
+  if (!placement_host_args(res, p, map, npages, dense) || cap < 0 || (cap && !rows)) return NMG_ERR_INVALID;
+  nmg::PlaceGroups g;
+  nmg::placement_object_groups(res->nb_entries, npages.data(), dense.data(), g);
+  std::vector<uint64_t> out;
+  nmg::placement_blocks_host(g, map, res->cells, res->nb_cells, res->nb_entries, out);
+  const int64_t n = (int64_t)(out.size() / 5);
+  if (std::min(n, cap)) memcpy(rows, out.data(), (size_t)std::min(n, cap) * 40);
+  return n;
 }
 
 extern "C" int nmg_report_host(const nmg_host_results* res, const nmg_object_meta* meta,

@@ -333,6 +333,32 @@ class Engine:
         self._c(lib.nmg_report_timeline(self.h, meta, C.byref(ro)))
         del keep
 
+    # ---- NUMA placement
+    def object_blocks(self, nb_nodes: int, thread_node=None, density_threshold: int = 8) -> np.ndarray:
+        """nmg_get_object_blocks: per object with dense page cells, the blocks
+        of consecutive pages to bind to one NUMA node, as u64 rows (entry,
+        node, start_page, end_page, count) sorted by (entry, start_page).
+        thread_node[rank] is the node of a thread (None: rank / (nb_threads /
+        nb_nodes)); a page counts when its dominant node has more than
+        density_threshold accesses."""
+        po, keep = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold)
+        n = lib.nmg_count_object_blocks(self.h, C.byref(po))
+        self._c(n)
+        rows = np.empty((n, 5), dtype=np.uint64)  # (every row written by the engine)
+        self._c(lib.nmg_get_object_blocks(self.h, C.byref(po), _ptr(rows, C.c_uint64), n))
+        del keep
+        return rows
+
+    def report_placement(self, output_dir: str, nb_nodes: int, thread_node=None, density_threshold: int = 8,
+                         online: bool = False):
+        """nmg_report_placement: <output_dir>/blocks.dat, the per-call-site
+        blocks in the format libnuma_run.so's custom mbind policy loads."""
+        meta, keep = build_meta(self.table)
+        ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
+        po, kmap = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold)
+        self._c(lib.nmg_report_placement(self.h, meta, C.byref(ro), C.byref(po)))
+        del keep, kmap
+
     # ---- multi-GPU merge helpers
     def array_size(self, which: int) -> int:
         return int(lib.nmg_array_size(self.h, which))
