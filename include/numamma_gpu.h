@@ -352,6 +352,60 @@ int nmg_set_timeline(nmg_engine *h, const struct nmg_timeline_options *tl);
 int64_t nmg_count_timeline_cells(nmg_engine *h);
 int nmg_get_timeline_cells(nmg_engine *h, uint32_t *rows /* [n][5] */, int64_t n);
 
+/* ---- page cost cells: per (entry, thread, page) one u64 cell beside the page
+ * histogram, summing over the matched samples of chosen memory levels either
+ * their number or their weight (the latency perf reports), so that a caller
+ * can tell which thread pays how much, on which page, for accesses that left
+ * the socket.
+ * The rule.  A matched SAMPLE of entry e, buffer thread t and access a
+ * (0 = read, 1 = write) is selected iff
+ *   (1 << a) & access_mask   is non-zero, and
+ *   sel(mem_lvl) & bucket_mask is non-zero,
+ * mem_lvl being the record's data_src.mem_lvl and sel(mem_lvl) the 18-bit
+ * bucket mask of update_counters -- bit b stands for nmg_mem_counters.b[b];
+ * per level group the hit bucket if PERF_MEM_LVL_HIT is set, else the miss
+ * bucket if PERF_MEM_LVL_MISS is set (HIT beats MISS), every group on its own
+ * -- with bit 18 (NMG_COST_NA) set when mem_lvl & PERF_MEM_LVL_NA.  A sample
+ * with mem_lvl == 0, or with neither HIT nor MISS and no NA, is never
+ * selected.  A selected sample adds 1 (NMG_COST_COUNT) or its weight
+ * (NMG_COST_WEIGHT) to the cell (e, t, page), page = (int)((addr -
+ * buffer_addr) / 4096) as the page histogram has it; a sample that hits
+ * several selected buckets adds once.  Only entries with dense page cells
+ * have cost cells (the timeline's and the placement's selection: huge ranges
+ * such as [stack] have none).
+ * nmg_set_page_cost allocates and zeroes the cells, cell (e, t, p) lying at
+ * the page histogram's own index: after nmg_set_objects, on a single-GPU
+ * engine created with NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST, with no stream
+ * open (NMG_ERR_STATE before a table exists or with a stream open;
+ * NMG_ERR_INVALID for options out of range, a multi-GPU handle or an engine
+ * without the two flags; NMG_ERR_CAPACITY, with the bytes needed in the
+ * error detail, when 8 * nb_threads * dense cells per thread exceeds
+ * budget_bytes).  o == NULL drops the cells; so does a later nmg_set_objects.
+ * Every analysis after it counts them (batch, streamed chunks, online
+ * alarms); they accumulate across analyses and nmg_reset_counters zeroes
+ * them.  nmg_update_objects is accepted for every table, a live host's
+ * growing one included: the cells are re-laid out with the histogram's (a
+ * grown layout past budget_bytes fails the update with NMG_ERR_CAPACITY and
+ * changes nothing).  The results snapshot does not hold them.
+ * The getters (NMG_ERR_STATE without cost cells) return the non-zero cells as
+ * (entry, thread, page, value) u64 rows in (entry, thread, page) order,
+ * compacted on the device and cached per results epoch. */
+#define NMG_COST_COUNT 0
+#define NMG_COST_WEIGHT 1
+#define NMG_COST_NA 0x40000u                          /* bucket mask bit 18 */
+#define NMG_COST_REMOTE ((1u << 5) | (1u << 6))       /* remote RAM hit, remote cache hit */
+#define NMG_COST_MEMORY ((1u << 4) | NMG_COST_REMOTE) /* + local RAM hit */
+struct nmg_page_cost_options {
+  uint32_t bucket_mask;  /* non-zero, < 2^19 */
+  uint32_t access_mask;  /* 1 = reads, 2 = writes, 3 = both; non-zero, <= 3 */
+  uint32_t metric;       /* NMG_COST_COUNT / NMG_COST_WEIGHT */
+  uint32_t reserved;     /* 0 */
+  uint64_t budget_bytes; /* cap on the cell array (0: default 1 GiB) */
+};
+int nmg_set_page_cost(nmg_engine *h, const struct nmg_page_cost_options *o);
+int64_t nmg_count_cost_cells(nmg_engine *h);
+int nmg_get_cost_cells(nmg_engine *h, uint64_t *rows /* [n][4] */, int64_t n);
+
 /* ---- results snapshot: the getters' results copied to host memory while
  * the next analysis runs (one engine of one GPU; not a multi-GPU handle, not
  * after nmg_set_buffer_counts).
@@ -499,6 +553,23 @@ int nmg_report_timeline_host(const struct nmg_host_results *res, const struct nm
                              const struct nmg_timeline_options *tl,
                              const uint32_t *rows, int64_t n);
 
+/*
+ * The cost cells per call site: one callsite_cost_<id>.dat in
+ * opts->output_dir for every call site with a non-zero cell inside its rows,
+ * <id> being the id nmg_report gives the site for the same results
+ * (opts->online as there).  The file is the matrix of
+ * callsite_counters_<id>.dat -- one line per page of the site's creating
+ * entry, one "\t<value>" per thread -- with the cost cells in place of the
+ * counts, a site's cell being the sum of its objects' cells at that page (a
+ * member's pages past the site's rows are dropped); stack sites are skipped.
+ * nmg_report_page_cost downloads the engine's rows and calls the host
+ * function, which needs no GPU: res as for nmg_report_host (cells are not
+ * read), rows as nmg_get_cost_cells returns them.
+ */
+int nmg_report_page_cost(nmg_engine *h, const struct nmg_object_meta *meta, const struct nmg_report_options *opts);
+int nmg_report_page_cost_host(const struct nmg_host_results *res, const struct nmg_object_meta *meta,
+                              const struct nmg_report_options *opts, const uint64_t *rows, int64_t n);
+
 /* ---- NUMA placement: which node each page of an object, or of a call site,
  * should live on, as blocks the reference's libnuma_run.so binds
  * (NUMAMMA_MBIND_POLICY=custom NUMAMMA_MBIND_FILE=<output_dir>/blocks.dat,
@@ -554,9 +625,11 @@ int nmg_report_timeline_host(const struct nmg_host_results *res, const struct nm
  *
  * Errors: NMG_ERR_INVALID for a NULL argument, nb_nodes outside 1..64, a
  * thread_node value >= nb_nodes, a NULL thread_node with nb_threads not a
- * multiple of nb_nodes, reserved != 0, or an engine without
- * NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST; NMG_ERR_STATE before
- * nmg_set_objects; NMG_ERR_IO when blocks.dat cannot be written.  Multi-GPU
+ * multiple of nb_nodes, a source other than the two below (and the cost
+ * source for nmg_report_placement_host: nmg_host_results has no cost rows), or
+ * an engine without NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST; NMG_ERR_STATE before
+ * nmg_set_objects, and for NMG_PLACE_PAGE_COST with no cost cells set;
+ * NMG_ERR_IO when blocks.dat cannot be written.  Multi-GPU
  * handles, streamed and online engines are accepted: the rule reads the
  * (merged) histogram only.  The object blocks are cached per results epoch
  * and options: nmg_count_object_blocks then nmg_get_object_blocks computes
@@ -564,13 +637,22 @@ int nmg_report_timeline_host(const struct nmg_host_results *res, const struct nm
  * (opts->online as there); nmg_report_placement_host computes the same file
  * from res->cells with no GPU (rank 0 of the one-process-per-GPU chain),
  * taking an entry's cells as dense when pages * nb_threads <= 2^24, the
- * engine's per-entry cap. */
+ * engine's per-entry cap.
+ *
+ * source: NMG_PLACE_PAGE_COUNTS folds the page histogram, as above.
+ * NMG_PLACE_PAGE_COST folds the page cost cells (nmg_set_page_cost) in their
+ * place: "the page cell (e, t, p)" is then the cost cell, cnt and the rows'
+ * count are cost sums, and density_threshold is compared with them.  The
+ * rule, the rows and blocks.dat are otherwise the same.  The cached object
+ * blocks are keyed by the source too. */
+#define NMG_PLACE_PAGE_COUNTS 0
+#define NMG_PLACE_PAGE_COST 2
 struct nmg_placement_options {
   uint32_t nb_nodes;            /* 1..64 */
   uint32_t density_threshold;   /* a page qualifies when its dominant node's count > this; the script's value is 8 */
   const uint32_t *thread_node;  /* [nb_threads], each < nb_nodes; NULL: rank / (nb_threads / nb_nodes),
                                    nb_threads % nb_nodes == 0 */
-  uint64_t reserved;            /* 0 */
+  uint64_t source;              /* NMG_PLACE_PAGE_COUNTS / NMG_PLACE_PAGE_COST; any other value is refused */
 };
 int64_t nmg_count_object_blocks(nmg_engine *h, const struct nmg_placement_options *p);
 int nmg_get_object_blocks(nmg_engine *h, const struct nmg_placement_options *p, uint64_t *rows /* [n][5] */, int64_t n);

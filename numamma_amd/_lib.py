@@ -150,14 +150,32 @@ class nmg_timeline_options(C.Structure):
 
 class nmg_placement_options(C.Structure):
     _fields_ = [("nb_nodes", C.c_uint32), ("density_threshold", C.c_uint32), ("thread_node", C.POINTER(C.c_uint32)),
-                ("reserved", C.c_uint64)]
+                ("source", C.c_uint64)]
 
 
-def placement_options(nb_threads, nb_nodes, thread_node=None, density_threshold=8, reserved=0):
+class nmg_page_cost_options(C.Structure):
+    _fields_ = [("bucket_mask", C.c_uint32), ("access_mask", C.c_uint32), ("metric", C.c_uint32),
+                ("reserved", C.c_uint32), ("budget_bytes", C.c_uint64)]
+
+
+NMG_COST_COUNT, NMG_COST_WEIGHT = 0, 1
+NMG_COST_NA = 0x40000
+NMG_COST_REMOTE = (1 << 5) | (1 << 6)
+NMG_COST_MEMORY = (1 << 4) | NMG_COST_REMOTE
+NMG_PLACE_PAGE_COUNTS, NMG_PLACE_PAGE_COST = 0, 2
+
+
+def placement_options(nb_threads, nb_nodes, thread_node=None, density_threshold=8, reserved=0, source=0):
     """(nmg_placement_options, the array it points into): thread_node None is
     the NULL map, rank / (nb_threads / nb_nodes); otherwise one node per thread
-    rank (the library reads nb_threads entries)."""
+    rank (the library reads nb_threads entries).  source: NMG_PLACE_PAGE_COUNTS
+    or NMG_PLACE_PAGE_COST; reserved= is the field's earlier name and sets the
+    same word."""
     import numpy as np
+
+    if reserved and source:
+        raise ValueError("reserved= and source= name the same field")
+    reserved = reserved or source
 
     tn = None if thread_node is None else np.ascontiguousarray(thread_node, dtype=np.uint32).reshape(-1)
     if tn is not None and tn.shape[0] != nb_threads:
@@ -230,6 +248,12 @@ _SIGS = {
     "nmg_report_timeline_host": (C.c_int, [C.POINTER(nmg_host_results), C.POINTER(nmg_object_meta),
                                            C.POINTER(nmg_report_options), C.POINTER(nmg_timeline_options), u32p,
                                            C.c_int64]),
+    "nmg_set_page_cost": (C.c_int, [H, C.POINTER(nmg_page_cost_options)]),
+    "nmg_count_cost_cells": (C.c_int64, [H]),
+    "nmg_get_cost_cells": (C.c_int, [H, u64p, C.c_int64]),
+    "nmg_report_page_cost": (C.c_int, [H, C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options)]),
+    "nmg_report_page_cost_host": (C.c_int, [C.POINTER(nmg_host_results), C.POINTER(nmg_object_meta),
+                                            C.POINTER(nmg_report_options), u64p, C.c_int64]),
     "nmg_count_object_blocks": (C.c_int64, [H, C.POINTER(nmg_placement_options)]),
     "nmg_get_object_blocks": (C.c_int, [H, C.POINTER(nmg_placement_options), u64p, C.c_int64]),
     "nmg_report_placement": (C.c_int, [H, C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options),

@@ -220,6 +220,59 @@ static_assert((uint64_t)kDensePageWindows * kWG * kLaneMaxWeight < (1ull << kPac
 // hashed object slots: flushed at least every kTableWindows windows
 static_assert((uint64_t)kTableWindows * kWG < (1ull << (64 - kPackShift)), "packed hashed count");
 static_assert((uint64_t)kTableWindows * kWG * kLaneMaxWeight <= (1ull << kPackShift), "packed hashed weight");
+
+// Page cost cells (Params::cost): the rule of include/numamma_gpu.h.  Whether
+// a matched SAMPLE of access `access` and level field lvl is selected, and
+// what it adds (0: nothing, a selected sample of weight 0 under
+// NMG_COST_WEIGHT included).
+__device__ __forceinline__ uint64_t cost_value(const Params& p, uint32_t access, uint32_t lvl, uint64_t w) {
+  const uint32_t sel = bucket_mask(lvl) | ((lvl & LVL_NA) ? (uint32_t)NMG_COST_NA : 0u);
+  if (!((1u << access) & p.cost_access_mask) || !(sel & p.cost_bucket_mask)) return 0;
+  return p.cost_metric == NMG_COST_WEIGHT ? w : 1ull;
+}
+
+// One add per lane with `on` of `value` into cost cell `index` (no-return u64
+// global atomics), merged like timeline_add: for up to `rounds` rounds the
+// lanes whose index equals the first pending lane's leave together and that
+// lane adds their summed value; the remaining lanes add singly.  Values from
+// kLaneMaxWeight on stay out of the u32 wave sum and add their own (64 x 2^23
+// < 2^32), as the level rows do.  WHOLE: every lane of the wave is here (the
+// extras block of local_kernel, behind its ballot), so the sum is
+// wave_sum_u32's DPP steps.  Otherwise the call sits in a diverged region
+// (process_sample, past its early returns) where the DPP steps would read
+// lanes that are off: the leader sums its group lane by lane with readlane,
+// which touches the group's lanes only.  rounds = 0 is the single-lane add
+// (direct_attribute: no cross-lane step).
+template <bool WHOLE>
+__device__ __forceinline__ void cost_add(const Params& p, bool on, uint64_t index, uint64_t value, uint32_t rounds) {
+  unsigned long long* c = reinterpret_cast<unsigned long long*>(p.cost);
+  if (rounds > 0) {
+    const uint32_t lane = __lane_id();
+    bool pend = on && value < kLaneMaxWeight;
+    uint64_t todo = __ballot(pend);
+    const uint32_t ilo = (uint32_t)index, ihi = (uint32_t)(index >> 32), v32 = pend ? (uint32_t)value : 0u;
+#pragma unroll 1
+    for (uint32_t r = 0; r < rounds && todo; r++) {
+      const uint32_t lead = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_ctzll(todo));
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)ilo, (int)lead);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)ihi, (int)lead);
+      const bool same = pend && ilo == lo && ihi == hi;  // (all still pending: a cell's lanes leave together)
+      const uint64_t sm = __ballot(same);
+      uint32_t s = 0;
+      if (WHOLE) {
+        s = wave_sum_u32(same ? v32 : 0u);
+      } else {
+        for (uint64_t m = sm; m; m &= m - 1) s += (uint32_t)__builtin_amdgcn_readlane((int)v32, __builtin_ctzll(m));
+      }
+      if (lane == lead) atomicAdd(c + index, (unsigned long long)s);
+      pend = pend && !same;
+      todo &= ~sm;
+    }
+    on = on && (pend || value >= kLaneMaxWeight);
+  }
+  if (on) atomicAdd(c + index, (unsigned long long)value);
+}
+
 // Only the hit buckets of the first kRegGroups level groups (L1, L2, L3: the
 // common case in PEBS data) live in registers; the other hit buckets and every
 // miss bucket are updated in LDS directly.  (Nine groups in registers left the

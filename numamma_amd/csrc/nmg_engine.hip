@@ -273,6 +273,8 @@ extern "C" int nmg_reset_counters(nmg_engine* h) {
   const uint32_t rgrid = (uint32_t)std::min<uint64_t>((longest + 256 * 16 - 1) / (256 * 16), (uint64_t)h->num_cus * 4);
   HIP_TRY(h, launch_reset(rgrid, h->stream, r));
   if (h->tl.on) HIP_TRY(h, hipMemsetAsync(h->tl.d_cells, 0, h->tl.ncells * 4, h->stream));
+  if (h->cost.on && h->cost.d_cells)
+    HIP_TRY(h, hipMemsetAsync(h->cost.d_cells, 0, h->tab.cells() * h->T * 8, h->stream));
   h->nreset++;
   h->counters_fresh = true;
   return NMG_OK;
@@ -563,6 +565,34 @@ extern "C" int nmg_report_timeline(nmg_engine* h, const nmg_object_meta* meta, c
   for (int64_t i = 0; i < n && !w.pos.empty(); i++) rows[5 * i] = w.pos[rows[5 * i]];  // (the writer groups by site: any order)
   std::string err;
   rc = write_timeline(&res, meta, opts, &h->tl.opt, rows.data(), n, err);
+  if (rc && !err.empty()) h->last_error = err;
+  return rc;
+}
+
+// The cost rows and the counters the call-site registry needs, handed to the
+// host writer (entries in the report's walk order, as nmg_report).
+extern "C" int nmg_report_page_cost(nmg_engine* h, const nmg_object_meta* meta, const nmg_report_options* opts) {
+  Range range("nmg_report_page_cost");
+  if (!h || (h->E && !meta)) return NMG_ERR_INVALID;
+  if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_report_page_cost before nmg_set_objects");
+  if (!h->cost.on) return fail(h, NMG_ERR_STATE, "no page cost cells set (nmg_set_page_cost)");
+  HostResults r;
+  int rc = engine_download(h, r, true, false);
+  if (rc) return rc;
+  std::vector<uint64_t> rows;
+  int64_t n = 0;
+  rc = collect_cost_cells(h, &rows, &n);
+  if (rc) return rc;
+  nmg_host_results res;
+  memset(&res, 0, sizeof(res));
+  res.nb_threads = h->T;
+  res.match_samples = 1;
+  WalkCounters w;
+  rc = walk_counters(h, r, res, w);
+  if (rc) return rc;
+  for (int64_t i = 0; i < n && !w.pos.empty(); i++) rows[4 * i] = w.pos[rows[4 * i]];  // (the writer groups by site: any order)
+  std::string err;
+  rc = write_page_cost(&res, meta, opts, rows.data(), n, err);
   if (rc && !err.empty()) h->last_error = err;
   return rc;
 }

@@ -265,6 +265,23 @@ struct Timeline {
   int64_t n = 0;
 };
 
+// The page cost cells (nmg_set_page_cost): one u64 array parallel to the page
+// histogram, cell (e, t, p) at t * tab.cells() + hist_base[e] + p -- the
+// histogram's index, so it has no layout of its own and grow_entries re-lays
+// it out with d_hist -- and the getters' rows.
+struct PageCost {
+  bool on = false;
+  nmg_page_cost_options opt{};
+  uint64_t budget = 0;             // bytes the array may take (opt.budget_bytes, or the default)
+  uint32_t rounds = kCostRounds;   // Params::cost_rounds
+  DevBuf<uint64_t> d_cells;        // [T * tab.cells()]; empty while the table has no dense cell
+  // rows of the current results epoch (nmg_count_cost_cells, then the copy
+  // out); the per-entry work arrays are cprep.lay's
+  DevBuf<uint64_t> d_rows;
+  uint64_t rows_epoch = 0;
+  int64_t n = 0;
+};
+
 // NUMA placement (nmg_placement.hip): groups on the device (PlaceParams'
 // arrays), and the engine's state -- the object groups of the current table,
 // the kernels' work arrays and the object blocks of the current results epoch.
@@ -284,6 +301,7 @@ struct PlaceState {
   DevBuf<uint64_t> d_rows;
   uint64_t rows_epoch = 0;
   uint32_t N = 0, D = 0;
+  uint64_t source = 0;  // nmg_placement_options::source of those rows
   std::vector<uint32_t> node;  // the thread -> node map of those rows (PlaceMap::node)
   int64_t n = 0;
 };
@@ -365,6 +383,7 @@ struct nmg_engine {
   DevBuf<uint64_t> d_scratch;          // [2] small device results (nmg_hist_pack / unpack) + range counts
   DevBuf<uint32_t> d_smatch;           // NMG_F_SAMPLE_MATCHES: per 8 B of the arena span
   Timeline tl;                         // nmg_set_timeline (dropped with the table)
+  PageCost cost;                       // nmg_set_page_cost (dropped with the table)
   PlaceState place;                    // nmg_count_object_blocks / nmg_report_placement
   uint64_t nreset = 0;
 
@@ -555,6 +574,8 @@ struct WalkCounters {  // walk_counters' arrays (empty while the walk order is t
 };
 int walk_counters(nmg_engine* h, const HostResults& r, nmg_host_results& res, WalkCounters& w);
 int timeline_prepare(nmg_engine* h);
+int cost_prepare(nmg_engine* h);
+int collect_cost_cells(nmg_engine* h, std::vector<uint64_t>* rows, int64_t* count);  // [n][4]
 int collect_timeline_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);  // [n][5]
 void* array_ptr(nmg_engine* h, int which, size_t* bytes);
 int scratch_u64(nmg_engine* h);

@@ -199,4 +199,8 @@ void placement_blocks_host(const PlaceGroups& g, const PlaceMap& m, const uint32
 int write_blocks(const std::vector<PlaceSite>& sites, const uint64_t* rows, int64_t n,
                  const nmg_report_options* opts, std::string& err);
 
+// callsite_cost_<id>.dat files from (entry, thread, page, value) rows
+int write_page_cost(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
+                    const uint64_t* rows, int64_t n, std::string& err);
+
 }  // namespace nmg

@@ -171,7 +171,25 @@ struct Params {
   uint64_t tl_t0;
   uint32_t tl_bin_shift, tl_nb_bins, tl_row_shift;
   uint32_t tl_rounds;  // timeline_add's merge rounds (kTlRounds)
+  // page cost cells (nmg_set_page_cost): u64 cells at the page histogram's
+  // index, thread * hist_cells + cell; null: off.  The rule is in
+  // include/numamma_gpu.h (cost_selected / cost_add in nmg_device.h).
+  uint64_t* cost;
+  uint32_t cost_bucket_mask, cost_access_mask, cost_metric;
+  uint32_t cost_rounds;  // cost_add's merge rounds (kCostRounds)
 };
+
+// merge rounds of cost_add (nmg_device.h) before the remaining lanes add
+// their own cell: Params::cost_rounds, kCostRounds unless the environment
+// variable NMG_COST_ROUNDS (0..64) says otherwise when the cells are set.
+// Measured at the configs[3] shard (tools/cost_timing.py), a
+// step of 2.60 ms without the cells: (NMG_COST_MEMORY, both, weight) 6.02 /
+// 5.78 / 5.51 / 5.53 ms at 0 / 1 / 4 / 64 rounds -- the fastest is the
+// default; 64 is within its spread.  A mask that selects nearly every record
+// (all buckets | N/A, count) puts the L1 hits of the hot objects on few
+// cells and keeps gaining: 37.5 / 33.5 / 21.0 / 9.7 ms; such a caller sets
+// NMG_COST_ROUNDS=64.
+constexpr uint32_t kCostRounds = 4;
 
 // DevEntry::pad1 of the by-id entries (Params::entries): the entry's first
 // timeline cell and its rows R, or kTlNone (no timeline, or the entry is not
@@ -258,6 +276,11 @@ hipError_t launch_cells_count(hipStream_t s, const uint32_t* hist, uint64_t hist
                               const uint64_t* base, const uint32_t* np, uint32_t E, uint32_t* cnt);
 hipError_t launch_cells_emit(hipStream_t s, const uint32_t* hist, uint64_t hist_cells, uint32_t T,
                              const uint64_t* base, const uint32_t* np, uint32_t E, const uint64_t* off, uint4* rows);
+// the same over the page cost cells (u64, at the histogram's index): rows of four u64
+hipError_t launch_cells_count(hipStream_t s, const uint64_t* cost, uint64_t hist_cells, uint32_t T,
+                              const uint64_t* base, const uint32_t* np, uint32_t E, uint32_t* cnt);
+hipError_t launch_cells_emit(hipStream_t s, const uint64_t* cost, uint64_t hist_cells, uint32_t T,
+                             const uint64_t* base, const uint32_t* np, uint32_t E, const uint64_t* off, uint64_t* rows);
 // timeline rows on the device (nmg_get_timeline_cells): the cell array in
 // segments of kTlSeg cells, per segment the number of non-zero cells, then
 // (after a scan) the (entry, bin, thread, row, count) rows at each segment's
@@ -275,6 +298,7 @@ hipError_t launch_tl_emit(hipStream_t s, const uint32_t* tl, uint64_t ncells, co
 // group g's page p is group page pg_off[g] + p, pg_off[G] of them in all.
 struct PlaceParams {
   const uint32_t* hist;  // the page histogram: cell (t, c) at t * hist_cells + c
+  const uint64_t* cost;  // NMG_PLACE_PAGE_COST: the page cost cells at the same index, folded instead (else null)
   uint64_t hist_cells;
   const uint32_t* thr;       // [T] thread ranks sorted by node
   const uint32_t* node_off;  // [N + 1] node n's ranks at thr[node_off[n] .. node_off[n + 1])

@@ -274,7 +274,7 @@ __device__ __forceinline__ void sub_stamp(SubTimer& st, int i) {
 // Process one decoded record (`valid` = it is a SAMPLE).  Every lane of the
 // wave calls this together (wave-level reductions inside); vmask / fmask are
 // the wave's SAMPLE and matched lanes.
-template <int MODE, bool TIMING>
+template <int MODE, bool TIMING, bool COST>
 __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAcc& acc, const Lookup& L, SubTimer& st,
                                                bool valid, bool shortrec, uint64_t ts, uint64_t addr,
                                                uint64_t w, uint64_t dsrc, uint32_t access,
@@ -367,6 +367,14 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
     const uint64_t pad = p.entries[e].pad1;
     const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
     timeline_add(p, pad != kTlNone, timeline_cell(p, pad, ts, th, page), p.tl_rounds);
+  }
+  // page cost cells: the histogram's cell of a selected sample (dense entries
+  // only).  COST: the instances for engines with cost cells set, so that the
+  // others are the code they were before the cells existed.
+  if (COST && p.cost) {
+    const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
+    const uint64_t v = m.hist != kHistSparse ? cost_value(p, access, lvl, w) : 0ull;
+    cost_add<false>(p, v != 0, uint64_t(th) * p.hist_cells + (m.hist + page), v, p.cost_rounds);
   }
 }
 
@@ -511,7 +519,7 @@ __device__ __forceinline__ void load_slot(const Params& p, const WinLane& w, con
   load_rec(p.data + off, w.pos, len, r);
 }
 
-template <bool TIMING, int MODE>
+template <bool TIMING, int MODE, bool COST>
 __global__ __launch_bounds__(kWG, 1) void attribute_kernel(Params p) {
   __shared__ uint4 s_tab[kTabBytes / 16];  // lookup structure (layouts at kTabBytes)
   __shared__ uint32_t s_list[kMaxList];
@@ -735,7 +743,7 @@ __global__ __launch_bounds__(kWG, 1) void attribute_kernel(Params p) {
     }
     uint64_t vm = 0, fm = 0;
     if (!(p.flags & kDbgLoadOnly))
-      process_sample<MODE, TIMING>(p, wc, acc, L, st, valid, shortrec, rec.ts, rec.addr, rec.w, rec.dsrc, d0.access, d0.thread_rank, d0, d1, rin1,
+      process_sample<MODE, TIMING, COST>(p, wc, acc, L, st, valid, shortrec, rec.ts, rec.addr, rec.w, rec.dsrc, d0.access, d0.thread_rank, d0, d1, rin1,
                            roff, vm, fm, sp);
     sub_stamp<TIMING>(st, 4);
     if (kSpec && (p.flags & NMG_F_MATCH_SAMPLES)) {
@@ -1253,18 +1261,20 @@ __global__ __launch_bounds__(256) void sparse_insert_kernel(uint64_t* keys, uint
 typedef void (*AttributeKernel)(Params);
 
 hipError_t launch_attribute(bool timing, int mode, uint32_t grid, hipStream_t s, const Params& p) {
-  static const AttributeKernel k[2][8] = {
-      {attribute_kernel<false, 0>, attribute_kernel<false, 1>, attribute_kernel<false, 2>, attribute_kernel<false, 3>,
-       attribute_kernel<false, 4>, attribute_kernel<false, 5>, attribute_kernel<false, 6>, attribute_kernel<false, 7>},
-      {attribute_kernel<true, 0>, attribute_kernel<true, 1>, attribute_kernel<true, 2>, attribute_kernel<true, 3>,
-       attribute_kernel<true, 4>, attribute_kernel<true, 5>, attribute_kernel<true, 6>, attribute_kernel<true, 7>}};
-  hipLaunchKernelGGL(k[timing ? 1 : 0][mode & 7], dim3(grid), dim3(kWG), 0, s, p);
+#define NMG_ATTR8(T, C)                                                                                      \
+  {attribute_kernel<T, 0, C>, attribute_kernel<T, 1, C>, attribute_kernel<T, 2, C>, attribute_kernel<T, 3, C>, \
+   attribute_kernel<T, 4, C>, attribute_kernel<T, 5, C>, attribute_kernel<T, 6, C>, attribute_kernel<T, 7, C>}
+  // [page cost cells set][timing][mode]
+  static const AttributeKernel k[2][2][8] = {{NMG_ATTR8(false, false), NMG_ATTR8(true, false)},
+                                             {NMG_ATTR8(false, true), NMG_ATTR8(true, true)}};
+#undef NMG_ATTR8
+  hipLaunchKernelGGL(k[p.cost ? 1 : 0][timing ? 1 : 0][mode & 7], dim3(grid), dim3(kWG), 0, s, p);
   return hipGetLastError();
 }
 
 int attribute_blocks_per_cu() {
   int bpc = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, attribute_kernel<false, 0>, kWG, 0) != hipSuccess || bpc <= 0)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (attribute_kernel<false, 0, false>), kWG, 0) != hipSuccess || bpc <= 0)
     bpc = 1;
   return bpc;
 }
@@ -1278,9 +1288,12 @@ hipError_t launch_tlog_reduce(uint32_t grid, hipStream_t s, const TlogParams& r)
 // Page-cell rows (the report's per-(entry, thread, page) counts): one wave per
 // entry, its T x np cells walked thread-major in 64-cell steps; a ballot
 // gives each non-zero cell its row.  Sparse entries (base == kHistSparse)
-// count 0 here: the host adds their rows from the sparse table.
+// count 0 here: the host adds their rows from the sparse table.  CELL: u32
+// (the page histogram; uint4 rows) or u64 (the page cost cells at the same
+// index; four u64 per row).
 
-__global__ __launch_bounds__(256) void cells_count_kernel(const uint32_t* hist, uint64_t hist_cells, uint32_t T,
+template <class CELL>
+__global__ __launch_bounds__(256) void cells_count_kernel(const CELL* hist, uint64_t hist_cells, uint32_t T,
                                                           const uint64_t* base, const uint32_t* np, uint32_t E,
                                                           uint32_t* cnt) {
   const uint32_t lane = threadIdx.x & 63;
@@ -1301,9 +1314,19 @@ __global__ __launch_bounds__(256) void cells_count_kernel(const uint32_t* hist, 
   }
 }
 
-__global__ __launch_bounds__(256) void cells_emit_kernel(const uint32_t* hist, uint64_t hist_cells, uint32_t T,
+__device__ __forceinline__ void cells_row(uint4* rows, uint64_t i, uint32_t e, uint32_t th, uint32_t p, uint32_t v) {
+  rows[i] = make_uint4(e, th, p, v);
+}
+__device__ __forceinline__ void cells_row(uint64_t* rows, uint64_t i, uint32_t e, uint32_t th, uint32_t p, uint64_t v) {
+  ulonglong2* r = reinterpret_cast<ulonglong2*>(rows + 4 * i);
+  r[0] = make_ulonglong2(e, th);
+  r[1] = make_ulonglong2(p, v);
+}
+
+template <class CELL, class ROW>
+__global__ __launch_bounds__(256) void cells_emit_kernel(const CELL* hist, uint64_t hist_cells, uint32_t T,
                                                          const uint64_t* base, const uint32_t* np, uint32_t E,
-                                                         const uint64_t* off, uint4* rows) {
+                                                         const uint64_t* off, ROW* rows) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t nw = gridDim.x * (blockDim.x / 64);
   for (uint32_t e = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; e < E; e += nw) {
@@ -1314,9 +1337,9 @@ __global__ __launch_bounds__(256) void cells_emit_kernel(const uint32_t* hist, u
     for (uint32_t i0 = 0; i0 < tot; i0 += 64) {
       const uint32_t i = i0 + lane;
       const uint32_t th = i / pg, p = i - th * pg;
-      const uint32_t v = i < tot ? hist[uint64_t(th) * hist_cells + b + p] : 0u;
+      const CELL v = i < tot ? hist[uint64_t(th) * hist_cells + b + p] : CELL(0);
       const uint64_t m = __ballot(v != 0);
-      if (v) rows[o + __popcll(m & ((1ull << lane) - 1))] = make_uint4(e, th, p, v);
+      if (v) cells_row(rows, o + __popcll(m & ((1ull << lane) - 1)), e, th, p, v);
       o += (uint64_t)__popcll(m);
     }
   }
@@ -1441,7 +1464,7 @@ hipError_t launch_copy_rows(hipStream_t s, const void* src, const uint64_t* n_pt
 hipError_t launch_cells_count(hipStream_t s, const uint32_t* hist, uint64_t hist_cells, uint32_t T,
                               const uint64_t* base, const uint32_t* np, uint32_t E, uint32_t* cnt) {
   const uint32_t grid = (uint32_t)std::min<uint64_t>((E + 3) / 4, 8192);
-  hipLaunchKernelGGL(cells_count_kernel, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, hist, hist_cells, T,
+  hipLaunchKernelGGL(cells_count_kernel<uint32_t>, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, hist, hist_cells, T,
                      base, np, E, cnt);
   return hipGetLastError();
 }
@@ -1449,8 +1472,25 @@ hipError_t launch_cells_count(hipStream_t s, const uint32_t* hist, uint64_t hist
 hipError_t launch_cells_emit(hipStream_t s, const uint32_t* hist, uint64_t hist_cells, uint32_t T,
                              const uint64_t* base, const uint32_t* np, uint32_t E, const uint64_t* off, uint4* rows) {
   const uint32_t grid = (uint32_t)std::min<uint64_t>((E + 3) / 4, 8192);
-  hipLaunchKernelGGL(cells_emit_kernel, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, hist, hist_cells, T,
+  hipLaunchKernelGGL((cells_emit_kernel<uint32_t, uint4>), dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, hist, hist_cells, T,
                      base, np, E, off, rows);
+  return hipGetLastError();
+}
+
+// the u64 instances: the page cost cells, (entry, thread, page, value) rows of four u64
+hipError_t launch_cells_count(hipStream_t s, const uint64_t* cost, uint64_t hist_cells, uint32_t T,
+                              const uint64_t* base, const uint32_t* np, uint32_t E, uint32_t* cnt) {
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((E + 3) / 4, 8192);
+  hipLaunchKernelGGL(cells_count_kernel<uint64_t>, dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, cost, hist_cells, T,
+                     base, np, E, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_cells_emit(hipStream_t s, const uint64_t* cost, uint64_t hist_cells, uint32_t T,
+                             const uint64_t* base, const uint32_t* np, uint32_t E, const uint64_t* off, uint64_t* rows) {
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((E + 3) / 4, 8192);
+  hipLaunchKernelGGL((cells_emit_kernel<uint64_t, uint64_t>), dim3(std::max<uint32_t>(grid, 1)), dim3(256), 0, s, cost,
+                     hist_cells, T, base, np, E, off, rows);
   return hipGetLastError();
 }
 

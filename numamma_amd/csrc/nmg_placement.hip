@@ -18,8 +18,10 @@ namespace nmg {
 // intermediate).  For a fixed (member, thread) the lanes of a wave that share
 // the group read consecutive cells.  Every index stays inside the histogram:
 // pg < m_np[m], and the host checks m_base[m] + m_np[m] <= hist_cells and
-// thr[k] < T.
-__global__ __launch_bounds__(256) void place_fold_kernel(PlaceParams p, uint64_t pages) {
+// thr[k] < T.  CELL: u32 folds the page histogram, u64 the page cost cells,
+// which lie at the same index.
+template <class CELL>
+__global__ __launch_bounds__(256) void place_fold_kernel(PlaceParams p, const CELL* cells, uint64_t pages) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < pages; i += gridDim.x * 256ull) {
     // the group g with pg_off[g] <= i < pg_off[g + 1] (i < pages = pg_off[G])
     uint32_t g = 0, len = p.G;
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void place_fold_kernel(PlaceParams p, uint64_t
       uint64_t s = 0;
       for (uint32_t m = m0; m < m1; m++) {
         if (pg >= p.m_np[m]) continue;
-        const uint32_t* cell = p.hist + p.m_base[m] + pg;
+        const CELL* cell = cells + p.m_base[m] + pg;
         for (uint32_t k = k0; k < k1; k++) s += cell[uint64_t(p.thr[k]) * p.hist_cells];
       }
       if (s > best) {  // (strict: the lowest node on a tie)
@@ -121,7 +123,8 @@ __global__ __launch_bounds__(256) void place_blocks_kernel(PlaceParams p) {
 
 hipError_t launch_place_fold(hipStream_t s, const PlaceParams& p, uint64_t pages) {
   const uint32_t grid = (uint32_t)std::min<uint64_t>((pages + 255) / 256, 1u << 20);
-  if (pages) hipLaunchKernelGGL(place_fold_kernel, dim3(grid), dim3(256), 0, s, p, pages);
+  if (pages && p.cost) hipLaunchKernelGGL(place_fold_kernel<uint64_t>, dim3(grid), dim3(256), 0, s, p, p.cost, pages);
+  else if (pages) hipLaunchKernelGGL(place_fold_kernel<uint32_t>, dim3(grid), dim3(256), 0, s, p, p.hist, pages);
   return hipGetLastError();
 }
 hipError_t launch_place_count(hipStream_t s, const PlaceParams& p) {
@@ -179,7 +182,8 @@ int upload_groups(nmg_engine* h, PlaceDev& d, const PlaceGroups& g, const std::v
 }
 
 // fold, count, scan, emit over the groups d: *n rows left in d_rows
-int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, DevBuf<uint64_t>& d_rows, int64_t* n) {
+int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, bool from_cost, DevBuf<uint64_t>& d_rows,
+               int64_t* n) {
   *n = 0;
   if (!d.G) return NMG_OK;
   PlaceState& S = h->place;
@@ -193,6 +197,7 @@ int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, DevBuf<uin
   HIP_TRY(h, S.d_part.reserve(scan_parts(d.G) + 1));
   PlaceParams p{};
   p.hist = h->cnt.d_hist;
+  p.cost = from_cost ? (const uint64_t*)h->cost.d_cells : nullptr;  // (cells exist: the groups have dense members)
   p.hist_cells = h->tab.cells();
   p.thr = S.d_thr;
   p.node_off = S.d_noff;
@@ -231,6 +236,8 @@ int placement_begin(nmg_engine* h, const nmg_placement_options* p, PlaceMap& map
   if ((h->flags & NMG_F_DEFAULT) != NMG_F_DEFAULT)
     return fail(h, NMG_ERR_INVALID, "placement needs NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST");
   if (!h->have_table) return fail(h, NMG_ERR_STATE, "placement before nmg_set_objects");
+  if (p->source == NMG_PLACE_PAGE_COST && !h->cost.on)
+    return fail(h, NMG_ERR_STATE, "placement from the page cost cells: none set (nmg_set_page_cost)");
   HIP_TRY(h, hipSetDevice(h->device));
   return nmg_synchronize(h);
 }
@@ -241,7 +248,8 @@ int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p) {
   int rc = placement_begin(h, p, map);
   if (rc) return rc;
   PlaceState& S = h->place;
-  if (S.rows_epoch == h->epoch && S.N == map.N && S.D == map.D && S.node == map.node) return NMG_OK;
+  if (S.rows_epoch == h->epoch && S.N == map.N && S.D == map.D && S.source == p->source && S.node == map.node)
+    return NMG_OK;
   if (S.obj_dirty) {  // (the table's groups: uploaded once per table)
     std::vector<uint64_t> npages, base;
     std::vector<uint8_t> dense;
@@ -253,11 +261,12 @@ int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p) {
     S.obj_dirty = false;
   }
   S.rows_epoch = 0;
-  rc = run_blocks(h, S.obj, map, S.d_rows, &S.n);
+  rc = run_blocks(h, S.obj, map, p->source == NMG_PLACE_PAGE_COST, S.d_rows, &S.n);
   if (rc) return rc;
   S.rows_epoch = h->epoch;
   S.N = map.N;
   S.D = map.D;
+  S.source = p->source;
   S.node = map.node;
   return NMG_OK;
 }
@@ -317,7 +326,7 @@ extern "C" int nmg_report_placement(nmg_engine* h, const nmg_object_meta* meta, 
     DevBuf<uint64_t> d_rows;
     int64_t n = 0;
     rc = upload_groups(h, d, g, base);
-    if (!rc) rc = run_blocks(h, d, map, d_rows, &n);
+    if (!rc) rc = run_blocks(h, d, map, p->source == NMG_PLACE_PAGE_COST, d_rows, &n);
     if (rc) return rc;
     rows.resize((size_t)n * 5);
     if (n) HIP_TRY(h, hipMemcpy(rows.data(), d_rows, (size_t)n * 40, hipMemcpyDeviceToHost));

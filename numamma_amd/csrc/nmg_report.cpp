@@ -515,11 +515,70 @@ int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const
   return NMG_OK;
 }
 
+// callsite_cost_<id>.dat per call site with a non-zero cell inside its rows
+// (the format is in include/numamma_gpu.h): the matrix of
+// callsite_counters_<id>.dat with the cost cells in it.  rows: (entry, thread,
+// page, value), any order; a site's cell sums its objects' cells, pages past
+// the site's rows dropped, as SiteHist::add drops them.
+int write_page_cost(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
+                    const uint64_t* rows, int64_t n, std::string& err) {
+  const bool online = opts && opts->online;
+  const uint64_t T = r->nb_threads;
+  Registry reg(meta);
+  if (r->match_samples) {
+    const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
+    if (rc) return rc;
+  }
+  // per site: (page * T + thread, value) of every row of its objects inside its rows
+  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> per(reg.sites.size());
+  for (int64_t i = 0; i < n; i++) {
+    const uint64_t* q = rows + 4 * i;
+    if (!q[3] || meta[q[0]].mem_type == kMemTypeStack) continue;
+    const int64_t si = reg.find((uint32_t)q[0]);
+    if (si < 0) continue;  // (an entry without matched samples has no cells)
+    const Site& s = reg.sites[si];
+    if (s.mem_type == kMemTypeStack || q[2] >= s.mem_info_buffer_size / kPageSize + 1) continue;
+    per[si].push_back({q[2] * T + q[1], q[3]});
+  }
+  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
+  mkdir(dir, S_IRWXU);
+  std::string line;
+  char cell[32];
+  for (size_t si = 0; si < per.size(); si++) {
+    auto& l = per[si];
+    if (l.empty()) continue;
+    std::sort(l.begin(), l.end());
+    char fn[4096];
+    snprintf(fn, sizeof(fn), "%s/callsite_cost_%d.dat", dir, (int)reg.sites[si].id);
+    FILE* f = fopen(fn, "w");
+    if (!f) {
+      err = std::string("cannot open ") + fn;
+      return NMG_ERR_IO;
+    }
+    const uint64_t nrows = reg.sites[si].mem_info_buffer_size / kPageSize + 1;
+    size_t i = 0;
+    for (uint64_t pg = 0; pg < nrows; pg++) {
+      line.clear();
+      for (uint64_t th = 0; th < T; th++) {
+        uint64_t v = 0;
+        for (; i < l.size() && l[i].first == pg * T + th; i++) v += l[i].second;
+        line.append(cell, snprintf(cell, sizeof(cell), "\t%" PRIu64, v));
+      }
+      line.push_back('\n');
+      fwrite(line.data(), 1, line.size(), f);
+    }
+    fclose(f);
+  }
+  return NMG_OK;
+}
+
 // ---- NUMA placement (the rule, the file and their differences from
 // scripts/counters_to_binding.py are in include/numamma_gpu.h)
 
 int placement_map(const nmg_placement_options* p, uint32_t T, PlaceMap& out) {
-  if (!p || p->nb_nodes < 1 || p->nb_nodes > 64 || p->reserved) return NMG_ERR_INVALID;
+  if (!p || p->nb_nodes < 1 || p->nb_nodes > 64 ||
+      (p->source != NMG_PLACE_PAGE_COUNTS && p->source != NMG_PLACE_PAGE_COST))
+    return NMG_ERR_INVALID;
   const uint32_t N = p->nb_nodes;
   if (!p->thread_node && T % N) return NMG_ERR_INVALID;
   std::vector<uint32_t>& node = out.node;
@@ -998,13 +1057,28 @@ extern "C" int nmg_report_timeline_host(const nmg_host_results* res, const nmg_o
   return rc;
 }
 
+extern "C" int nmg_report_page_cost_host(const nmg_host_results* res, const nmg_object_meta* meta,
+                                         const nmg_report_options* opts, const uint64_t* rows, int64_t n) {
+  if (!res || n < 0 || (n && !rows) ||
+      (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight || !res->buffer_size)) ||
+      res->nb_threads > NMG_MAX_THREADS)
+    return NMG_ERR_INVALID;
+  for (int64_t i = 0; i < n; i++)
+    if (rows[4 * i] >= res->nb_entries || rows[4 * i + 1] >= res->nb_threads) return NMG_ERR_INVALID;
+  std::string err;
+  int rc = nmg::write_page_cost(res, meta, opts, rows, n, err);
+  if (rc && !err.empty()) fprintf(stderr, "nmg_report_page_cost: %s\n", err.c_str());
+  return rc;
+}
+
 namespace {
 // the host's view of the page cells: an entry's pages, and whether the engine
 // keeps them dense (CellCursor::place's per-entry cap; budgets aside)
 bool placement_host_args(const nmg_host_results* res, const nmg_placement_options* p, nmg::PlaceMap& map,
                          std::vector<uint64_t>& npages, std::vector<uint8_t>& dense) {
   if (!res || (res->nb_entries && !res->buffer_size) || (res->nb_cells && !res->cells) || res->nb_cells < 0 ||
-      res->nb_threads > NMG_MAX_THREADS || nmg::placement_map(p, res->nb_threads, map))
+      res->nb_threads > NMG_MAX_THREADS || nmg::placement_map(p, res->nb_threads, map) ||
+      p->source != NMG_PLACE_PAGE_COUNTS)  // (nmg_host_results has no cost rows)
     return false;
   for (int64_t i = 0; i < res->nb_cells; i++)
     if (res->cells[4 * i] >= res->nb_entries || (i && res->cells[4 * i] < res->cells[4 * i - 4])) return false;

@@ -201,6 +201,27 @@ static void place_sparse_rows(const uint64_t* kv, uint64_t n, const std::vector<
   }
 }
 
+// the table's cell layout in cprep.lay, uploaded once per table (the page
+// cells' and the page cost cells' row passes)
+static int cprep_layout(nmg_engine* h) {
+  const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
+  auto& P = h->cprep;
+  CellLayout& C = P.lay;
+  int rc = C.ensure(h, E, nsent);
+  if (rc) return rc;
+  if (C.meta_dirty) {
+    std::vector<uint32_t> np;
+    cell_layout_host(h, np, P.sent_entry);
+    if (E) {
+      HIP_TRY(h, hipMemcpy(C.d_base, h->tab.hist_base.data(), E * 8, hipMemcpyHostToDevice));
+      HIP_TRY(h, hipMemcpy(C.d_np, np.data(), E * 4, hipMemcpyHostToDevice));
+    }
+    if (nsent) HIP_TRY(h, hipMemcpy(C.d_sent, h->tab.sparse_entries.data(), nsent * 4, hipMemcpyHostToDevice));
+    C.meta_dirty = false;
+  }
+  return NMG_OK;
+}
+
 // Every non-zero (entry, thread, page) cell, entries in id order, each
 // entry's cells in (thread, page) order.  On the device, in buffers kept
 // across calls (the table's cell layout uploaded once per table): dense cells
@@ -227,18 +248,8 @@ int cells_prepare(nmg_engine* h) {
   const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   auto& P = h->cprep;
   CellLayout& C = P.lay;
-  rc = C.ensure(h, E, nsent);
+  rc = cprep_layout(h);
   if (rc) return rc;
-  if (C.meta_dirty) {  // (the table's cell layout)
-    std::vector<uint32_t> np;
-    cell_layout_host(h, np, P.sent_entry);
-    if (E) {
-      HIP_TRY(h, hipMemcpy(C.d_base, h->tab.hist_base.data(), E * 8, hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(C.d_np, np.data(), E * 4, hipMemcpyHostToDevice));
-    }
-    if (nsent) HIP_TRY(h, hipMemcpy(C.d_sent, h->tab.sparse_entries.data(), nsent * 4, hipMemcpyHostToDevice));
-    C.meta_dirty = false;
-  }
   lap("meta");
   // sparse cells: compacted on the device (sparse_download, which leaves
   // them in d_sparse_ck); cells_fill places their rows
@@ -284,6 +295,63 @@ int cells_prepare(nmg_engine* h) {
   if (timing) fprintf(stderr, "cells_prepare: %llu rows\n", (unsigned long long)n);
   P.n = (int64_t)n;
   h->cells_epoch = h->epoch;
+  return NMG_OK;
+}
+
+// ---- page cost rows: the page cells' count / scan / emit over the u64 array
+// (same index, so cprep's layout and per-entry work arrays serve; a pass ends
+// before it returns, so the two do not meet).  The rows stay on the device
+// (cost.d_rows) until copied out, cached per results epoch -- the options are
+// the cells' own: nmg_set_page_cost bumps the epoch.
+int cost_prepare(nmg_engine* h) {
+  PageCost& c = h->cost;
+  if (!c.on) return fail(h, NMG_ERR_STATE, "no page cost cells set (nmg_set_page_cost)");
+  if (c.rows_epoch == h->epoch) return NMG_OK;
+  int rc = nmg_synchronize(h);
+  if (rc) return rc;
+  rc = cprep_layout(h);
+  if (rc) return rc;
+  CellLayout& C = h->cprep.lay;
+  const uint64_t E = h->E;
+  uint64_t n = 0;
+  if (E && c.d_cells) {
+    hipStream_t st = h->stream;
+    HIP_TRY(h, launch_cells_count(st, c.d_cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
+    HIP_TRY(h, launch_scan_u32(st, C.d_cnt, E, C.d_off, C.d_part));
+    HIP_TRY(h, hipMemcpyAsync(&n, C.d_off + E, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (n) {
+      HIP_TRY(h, c.d_rows.reserve(n * 4));
+      HIP_TRY(h, launch_cells_emit(st, c.d_cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off, c.d_rows));
+      HIP_TRY(h, hipStreamSynchronize(st));
+    }
+  }
+  c.n = (int64_t)n;
+  c.rows_epoch = h->epoch;
+  return NMG_OK;
+}
+
+int collect_cost_cells(nmg_engine* h, std::vector<uint64_t>* rows, int64_t* count) {
+  int rc = cost_prepare(h);
+  if (rc) return rc;
+  *count = h->cost.n;
+  rows->resize((size_t)h->cost.n * 4);
+  if (h->cost.n) HIP_TRY(h, hipMemcpy(rows->data(), h->cost.d_rows, (size_t)h->cost.n * 32, hipMemcpyDeviceToHost));
+  return NMG_OK;
+}
+
+extern "C" int64_t nmg_count_cost_cells(nmg_engine* h) {
+  if (!h) return NMG_ERR_INVALID;
+  int rc = cost_prepare(h);
+  return rc ? rc : h->cost.n;
+}
+
+extern "C" int nmg_get_cost_cells(nmg_engine* h, uint64_t* rows, int64_t n) {
+  if (!h || (n && !rows)) return NMG_ERR_INVALID;
+  int rc = cost_prepare(h);
+  if (rc) return rc;
+  if (h->cost.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
+  if (n) HIP_TRY(h, hipMemcpy(rows, h->cost.d_rows, (size_t)n * 32, hipMemcpyDeviceToHost));
   return NMG_OK;
 }
 

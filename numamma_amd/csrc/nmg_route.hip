@@ -95,8 +95,9 @@ __device__ __forceinline__ uint32_t raw_mem_lvl(const uint8_t* data, uint64_t po
 // only taken when a workgroup's samples outgrow its pool (SAMPLE records
 // shorter than 40 B, or the kDbgTinyPool test switch).  lvl = the record's
 // data_src.mem_lvl (read with NMG_F_OBJECT_LEVELS only); slot = its buffer's
-// index in p.sbufs (analysis order).  TL: the caller's instance serves engines
-// with a timeline set (route2_kernel has one of each).
+// index in p.sbufs (analysis order; also read with page cost cells set).  TL:
+// the caller's instance serves engines with a timeline or page cost cells set
+// (route2_kernel has one of each).
 template <bool TL>
 __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr, uint64_t ts, uint64_t w, uint32_t th,
                                                  uint32_t acc, uint32_t lvl, uint64_t seq, uint32_t off,
@@ -150,6 +151,10 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
   if (TL && p.tl) {  // access timeline: this lane's own add (the callers' lanes are diverged; no merge here)
     const uint64_t pad = p.entries[e].pad1;
     timeline_add(p, pad != kTlNone, timeline_cell(p, pad, ts, th, page), 0);
+  }
+  if (TL && p.cost && m.hist != kHistSparse) {  // page cost cells: again the lane's own add
+    const uint64_t v = cost_value(p, acc, lvl, w);
+    cost_add<false>(p, v != 0, uint64_t(th) * p.hist_cells + m.hist + page, v, 0);
   }
 }
 
@@ -1008,7 +1013,7 @@ __global__ __launch_bounds__(256) void overflow_kernel(RouteParams rp) {
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     XRec xr = x_decode(rp.xl, rp.ovfx[i], rp.ovf16[i]);
     if (xr.esc) x_resolve(xr, rp.xl, rp.p.data, rp.p.sbufs);
-    const uint32_t lvl = (rp.p.flags & NMG_F_OBJECT_LEVELS)
+    const uint32_t lvl = ((rp.p.flags & NMG_F_OBJECT_LEVELS) || rp.p.cost)
                              ? raw_mem_lvl(rp.p.data, rp.p.sbufs[xr.g(rp.xl)].offset + xr.off(rp.xl))
                              : 0u;
     direct_attribute<true>(rp.p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
@@ -1205,7 +1210,7 @@ __device__ __forceinline__ int32_t match_older_pos(const Params& p, uint32_t fir
 
 // PACKED: an online table with packed page cells (LocalParams::pe_cmap; a
 // variant of its own, so that the offline table's flush carries none of it).
-// EXTRA: the outputs of NMG_F_OBJECT_LEVELS, NMG_F_SAMPLE_MATCHES and the access timeline (the
+// EXTRA: the outputs of NMG_F_OBJECT_LEVELS, NMG_F_SAMPLE_MATCHES, the access timeline and the page cost cells (the
 // extras block at the end of `process`; again a variant of its own: the
 // instances without it are the code they were before it existed)
 template <bool TIMING, bool PACKED, bool EXTRA>
@@ -1646,10 +1651,11 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         // applies.
         const bool lev = (p.flags & NMG_F_OBJECT_LEVELS) != 0;
         const bool tlon = p.tl != nullptr;  // access timeline set: the matched records' cells
+        const bool cost = p.cost != nullptr;  // page cost cells set: the matched records' level and cell
         bool need[kLC], any = false;
 #pragma unroll
         for (int j = 0; j < kLC; j++) {
-          need[j] = valid[j] && (p.smatch != nullptr || ((lev || tlon) && erel[j] >= 0));
+          need[j] = valid[j] && (p.smatch != nullptr || ((lev || tlon || cost) && erel[j] >= 0));
           any |= need[j];
         }
         if (__ballot(any)) {
@@ -1667,9 +1673,9 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
             const bool hit = erel[j] >= 0;
             if (hit) eid[j] = entry_id(lp, pi.e0 + (uint32_t)erel[j]);
             if (p.smatch) p.smatch[pos >> 3] = hit ? (uint32_t)eid[j] + 1u : 0u;
-            if (lev && hit) {
+            if ((lev || cost) && hit) {  // (one load serves both)
               lvl[j] = raw_mem_lvl(p.data, pos);
-              row[j] = true;
+              row[j] = lev;
             }
           }
           // The level rows.  A chunk holds one partition's records, and a hot
@@ -1714,6 +1720,23 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
               const uint64_t ft = xr[j].esc ? ts[j] : lp.xl.tbase + ts[j];
               timeline_add(p, pad[j] != kTlNone,
                            timeline_cell(p, pad[j], ft, xr[j].th, uint32_t(int(pofs[j] / kPageSize))), p.tl_rounds);
+            }
+          }
+          // The page cost cells (wave-uniform here too).  The entry's first
+          // histogram cell is in its by-id record, the 64 B the timeline's
+          // pad1 comes from; the weight is the compact record's (escaped: the
+          // re-read one).
+          if (cost) {
+            uint64_t hb[kLC];
+#pragma unroll
+            for (int j = 0; j < kLC; j++)
+              hb[j] = need[j] && erel[j] >= 0 ? p.entries[eid[j]].hist : kHistSparse;
+#pragma unroll
+            for (int j = 0; j < kLC; j++) {
+              const uint64_t v = hb[j] != kHistSparse ? cost_value(p, xr[j].acc, lvl[j], w[j]) : 0ull;
+              cost_add<true>(p, v != 0,
+                             uint64_t(xr[j].th) * p.hist_cells + hb[j] + uint32_t(int(pofs[j] / kPageSize)), v,
+                             p.cost_rounds);
             }
           }
           vm_drain();
@@ -1894,9 +1917,9 @@ __global__ __launch_bounds__(kWG) void found_kernel(FoundParams r) {
 // launchers
 
 hipError_t launch_route(uint32_t grid, hipStream_t s, const RouteParams& r) {
-  // (TL: an instance of its own for engines with a timeline set, so that the
-  // other one is the code it was before the timeline existed)
-  const bool timing = (r.p.flags & kDbgRouteTiming) != 0, tl = r.p.tl != nullptr;
+  // (TL: an instance of its own for engines with a timeline or page cost cells
+  // set, so that the other one is the code it was before either existed)
+  const bool timing = (r.p.flags & kDbgRouteTiming) != 0, tl = r.p.tl != nullptr || r.p.cost != nullptr;
   if (timing && tl) hipLaunchKernelGGL((route2_kernel<true, true>), dim3(grid), dim3(kR2WG), 0, s, r);
   else if (timing) hipLaunchKernelGGL((route2_kernel<true, false>), dim3(grid), dim3(kR2WG), 0, s, r);
   else if (tl) hipLaunchKernelGGL((route2_kernel<false, true>), dim3(grid), dim3(kR2WG), 0, s, r);
@@ -1934,7 +1957,8 @@ static void launch_local_as(bool extra, uint32_t grid, hipStream_t s, const Loca
 // the extras variant for engines with per-object levels or per-sample matches
 hipError_t launch_local(uint32_t grid, hipStream_t s, const LocalParams& r) {
   const bool timing = (r.p.flags & kDbgLocalTiming) != 0, packed = r.pe_cmap != nullptr;
-  const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr || r.p.tl != nullptr;
+  const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr || r.p.tl != nullptr ||
+                     r.p.cost != nullptr;
   if (packed) {
     if (timing) launch_local_as<true, true>(extra, grid, s, r);
     else launch_local_as<false, true>(extra, grid, s, r);

@@ -648,6 +648,13 @@ Params base_params(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, co
     p.tl_row_shift = h->tl.opt.row_shift;
     p.tl_rounds = h->tl.rounds;
   }
+  if (h->cost.on) {
+    p.cost = h->cost.d_cells;  // (null while the table has no dense cell: nothing to count)
+    p.cost_bucket_mask = h->cost.opt.bucket_mask;
+    p.cost_access_mask = h->cost.opt.access_mask;
+    p.cost_metric = h->cost.opt.metric;
+    p.cost_rounds = h->cost.rounds;
+  }
   return p;
 }
 

@@ -428,6 +428,7 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
   free_table(h);  // (released before the new ones are allocated: no second table's worth of HBM)
   h->cnt = Counters();
   h->tl = Timeline();  // (a timeline is laid out for one table)
+  h->cost = PageCost();  // (and so are the page cost cells)
   h->lk.K = nb_keys;
   h->E = nb_entries;
 
@@ -551,6 +552,52 @@ extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
   return NMG_OK;
 }
 
+// The page cost cells for the current table (the rule is in
+// include/numamma_gpu.h): one u64 per cell of the page histogram, at its
+// index, zeroed.  Nothing in the table changes: the kernels find a cell from
+// the entry's histogram base, which they have.
+extern "C" int nmg_set_page_cost(nmg_engine* h, const nmg_page_cost_options* o) {
+  if (!h) return NMG_ERR_INVALID;
+  h->epoch++;
+  if (h->multi || !h->workers.empty()) return fail(h, NMG_ERR_INVALID, "nmg_set_page_cost: not on a multi-GPU handle");
+  constexpr uint32_t kNeed = NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST;
+  if ((h->flags & kNeed) != kNeed)
+    return fail(h, NMG_ERR_INVALID, "nmg_set_page_cost needs an engine created with NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST");
+  if (o && (o->bucket_mask == 0 || o->bucket_mask >= (1u << 19) || o->access_mask == 0 || o->access_mask > 3 ||
+            o->metric > NMG_COST_WEIGHT || o->reserved != 0))
+    return fail(h, NMG_ERR_INVALID, "nmg_set_page_cost: option out of range (bucket_mask 1..2^19 - 1, access_mask 1..3, "
+                                    "metric 0 or 1, reserved 0)");
+  if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_set_page_cost before nmg_set_objects");
+  if (h->streaming) return fail(h, NMG_ERR_STATE, "nmg_set_page_cost while a stream is open");
+  HIP_TRY(h, hipSetDevice(h->device));
+  int rc = route_settle(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // launches in flight add to the cells
+  if (!o) {
+    h->cost = PageCost();
+    return NMG_OK;
+  }
+  PageCost c;
+  c.opt = *o;
+  c.budget = o->budget_bytes ? o->budget_bytes : (1ull << 30);
+  if (const char* r = getenv("NMG_COST_ROUNDS")) c.rounds = (uint32_t)std::min(64, std::max(0, atoi(r)));  // (see kCostRounds)
+  const uint64_t ncells = h->tab.cells() * h->T;  // (within the histogram's budget: no overflow)
+  if (ncells * 8 > c.budget) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "nmg_set_page_cost: the cells need %llu bytes (budget %llu)",
+             (unsigned long long)(ncells * 8), (unsigned long long)c.budget);
+    return fail(h, NMG_ERR_CAPACITY, msg);
+  }
+  if (ncells) {
+    HIP_TRY(h, c.d_cells.alloc(ncells));
+    HIP_TRY(h, hipMemsetAsync(c.d_cells, 0, ncells * 8, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  c.on = true;
+  h->cost = std::move(c);
+  return NMG_OK;
+}
+
 // A live --online-analysis table (nmg_update_objects) may hold entries the
 // engine has not seen: objects created since the previous alarm (ids E ..
 // newE - 1, _init_mem_info's next id, mem_analyzer.c:567-568, with their
@@ -601,9 +648,17 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
     }
   }
   const uint64_t cells = tab.cur.cells = tab.cur.padded_cells();
+  // the page cost cells follow the histogram's layout, within their own budget
+  const bool with_cost = h->cost.on;
+  if (with_cost && cells * T * 8 > h->cost.budget) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "nmg_update_objects: the page cost cells need %llu bytes (budget %llu)",
+             (unsigned long long)(cells * T * 8), (unsigned long long)h->cost.budget);
+    return fail_rb(NMG_ERR_CAPACITY, msg);
+  }
   // id-indexed counters, re-laid out for newE entries
   const uint64_t n_sum = sum64_words(newE, levels), n_min = min64_words(newE);
-  DevBuf<uint64_t> sum, mn, skeys;
+  DevBuf<uint64_t> sum, mn, skeys, cost;
   DevBuf<uint32_t> hist, svals, sdirty;
   DevBuf<unsigned long long> pk;
   DevBuf<DevEntry> ent;
@@ -618,6 +673,7 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
   if ((e = mn.alloc(n_min)) != hipSuccess) return undo(e, "ordinals");
   if (cells && cells * T != oldCells * T && (e = hist.alloc(cells * T)) != hipSuccess)
     return undo(e, "page histogram");
+  if (hist && with_cost && (e = cost.alloc(cells * T)) != hipSuccess) return undo(e, "page cost cells");
   if (newE > kObjSlots && (e = pk.alloc((size_t)newE * 2)) != hipSuccess) return undo(e, "packed counters");
   if ((e = ent.alloc(newE)) != hipSuccess) return undo(e, "entries");
   hipStream_t st = h->stream;
@@ -659,6 +715,19 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
            (e = hipMemset2DAsync(hist + m.hist, cells * 4, 0, m.np * 4, T, st)) != hipSuccess))
         return undo(e, "page cells of a grown object");
   }
+  if (cost) {  // the same re-layout with 8-byte cells
+    const uint64_t* ocost = h->cost.d_cells;
+    if ((e = hipMemsetAsync(cost, 0, cells * T * 8, st)) != hipSuccess ||
+        (oldCells && ocost && (e = hipMemcpy2DAsync(cost, cells * 8, ocost, oldCells * 8, oldCells * 8, T,
+                                                    hipMemcpyDeviceToDevice, st)) != hipSuccess))
+      return undo(e, "page cost re-layout");
+    for (const Old& m : changed)
+      if (m.hist != tab.hist_base[m.id] &&
+          ((e = hipMemcpy2DAsync(cost + tab.hist_base[m.id], cells * 8, cost + m.hist, cells * 8, m.np * 8, T,
+                                 hipMemcpyDeviceToDevice, st)) != hipSuccess ||
+           (e = hipMemset2DAsync(cost + m.hist, cells * 8, 0, m.np * 8, T, st)) != hipSuccess))
+        return undo(e, "page cost cells of a grown object");
+  }
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return undo(e, "re-layout");
   // commit: the old arrays are released as the new ones move in
   if (!h->lk.own_chain) h->lk.chain = ent;  // (the table order is still the id order)
@@ -667,6 +736,7 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
   h->cnt.d_pk64 = std::move(pk);
   h->d_entries = std::move(ent);
   if (hist) h->cnt.d_hist = std::move(hist);
+  if (cost) h->cost.d_cells = std::move(cost);
   h->cnt.set_sizes(newE, levels);
   h->E = newE;
   if (new_sparse) {

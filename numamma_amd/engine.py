@@ -333,15 +333,46 @@ class Engine:
         self._c(lib.nmg_report_timeline(self.h, meta, C.byref(ro)))
         del keep
 
+    # ---- page cost cells
+    def set_page_cost(self, bucket_mask: Optional[int] = _lib.NMG_COST_MEMORY, access_mask: int = 3,
+                      metric: int = _lib.NMG_COST_WEIGHT, budget_bytes: int = 0, reserved: int = 0):
+        """nmg_set_page_cost: one u64 cell per (object, thread, page) summing,
+        over the matched samples whose memory level falls in bucket_mask and
+        whose access in access_mask, 1 or the sample's weight; counted by
+        every analysis from now on.  set_page_cost(None) drops the cells."""
+        if bucket_mask is None:
+            self._c(lib.nmg_set_page_cost(self.h, None))
+            return
+        o = _lib.nmg_page_cost_options(bucket_mask, access_mask, metric, reserved, budget_bytes)
+        self._c(lib.nmg_set_page_cost(self.h, C.byref(o)))
+
+    def cost_cells(self) -> np.ndarray:
+        """The non-zero cost cells as u64 (entry, thread, page, value) rows,
+        sorted by (entry, thread, page)."""
+        n = lib.nmg_count_cost_cells(self.h)
+        self._c(n)
+        rows = np.empty((n, 4), dtype=np.uint64)  # (every row written by the engine)
+        self._c(lib.nmg_get_cost_cells(self.h, _ptr(rows, C.c_uint64), n))
+        return rows
+
+    def report_page_cost(self, output_dir: str, online: bool = False):
+        """nmg_report_page_cost: callsite_cost_<id>.dat per call site."""
+        meta, keep = build_meta(self.table)
+        ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
+        self._c(lib.nmg_report_page_cost(self.h, meta, C.byref(ro)))
+        del keep
+
     # ---- NUMA placement
-    def object_blocks(self, nb_nodes: int, thread_node=None, density_threshold: int = 8) -> np.ndarray:
+    def object_blocks(self, nb_nodes: int, thread_node=None, density_threshold: int = 8,
+                      source: int = 0) -> np.ndarray:
         """nmg_get_object_blocks: per object with dense page cells, the blocks
         of consecutive pages to bind to one NUMA node, as u64 rows (entry,
         node, start_page, end_page, count) sorted by (entry, start_page).
         thread_node[rank] is the node of a thread (None: rank / (nb_threads /
         nb_nodes)); a page counts when its dominant node has more than
-        density_threshold accesses."""
-        po, keep = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold)
+        density_threshold accesses.  source = NMG_PLACE_PAGE_COST folds the
+        page cost cells (set_page_cost) instead of the counts."""
+        po, keep = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold, source=source)
         n = lib.nmg_count_object_blocks(self.h, C.byref(po))
         self._c(n)
         rows = np.empty((n, 5), dtype=np.uint64)  # (every row written by the engine)
@@ -350,12 +381,13 @@ class Engine:
         return rows
 
     def report_placement(self, output_dir: str, nb_nodes: int, thread_node=None, density_threshold: int = 8,
-                         online: bool = False):
+                         online: bool = False, source: int = 0):
         """nmg_report_placement: <output_dir>/blocks.dat, the per-call-site
-        blocks in the format libnuma_run.so's custom mbind policy loads."""
+        blocks in the format libnuma_run.so's custom mbind policy loads
+        (source as for object_blocks)."""
         meta, keep = build_meta(self.table)
         ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
-        po, kmap = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold)
+        po, kmap = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold, source=source)
         self._c(lib.nmg_report_placement(self.h, meta, C.byref(ro), C.byref(po)))
         del keep, kmap
 

@@ -136,6 +136,22 @@ def report_timeline_host(res: RawResults, table, output_dir: str, rows: np.ndarr
     del keep, kmeta
 
 
+def report_page_cost_host(res: RawResults, table, output_dir: str, rows: np.ndarray, online: bool = False) -> None:
+    """nmg_report_page_cost_host(): callsite_cost_<id>.dat files from host
+    arrays (no GPU involved).  rows: u64 (entry, thread, page, value) as
+    Engine.cost_cells() returns them."""
+    from . import _lib
+    from .engine import build_meta
+
+    hr, keep = _host_results(res, table, np.zeros(res.nb_buffers, dtype=np.uint64), True)
+    meta, kmeta = build_meta(table)
+    ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 4)
+    _lib.check(_lib.lib.nmg_report_page_cost_host(C.byref(hr), meta, C.byref(ro),
+                                                  rows.ctypes.data_as(C.POINTER(C.c_uint64)), rows.shape[0]))
+    del keep, kmeta
+
+
 def report_placement_host(res: RawResults, table, output_dir: str, nb_nodes: int, thread_node=None,
                           density_threshold: int = 8, online: bool = False) -> None:
     """nmg_report_placement_host(): <output_dir>/blocks.dat from host arrays (no
