@@ -291,10 +291,20 @@ int nmg_set_device_buffers(nmg_engine *h, const void *d_data, const uint64_t *of
 /* Enqueue attribution of every submitted buffer (stages host buffers H2D
  * first).  Asynchronous; counters accumulate across calls. */
 int nmg_analyze(nmg_engine *h);
+/* Wait for the enqueued analyses.  A malformed record stream is reported here
+ * (NMG_ERR_ZERO_SIZE / NMG_ERR_TRUNCATED / NMG_ERR_UNALIGNED; the detail names
+ * the buffer in analysis order and the byte offset): the first malformed
+ * record in analysis order, whatever the number of malformed buffers, of
+ * analyses and of streamed chunks since the last nmg_reset_counters.  The
+ * reference aborts there, so the counters of such an analysis are
+ * unspecified, and the error is reported by every nmg_synchronize until
+ * nmg_reset_counters clears it. */
 int nmg_synchronize(nmg_engine *h);
-/* Zero every counter (global, per buffer, per object, page histogram); per
- * buffer counts replaced by nmg_set_buffer_counts are dropped (the engine's own
- * buffers again). */
+/* Zero every counter (global, per buffer, per object, page histogram) and
+ * clear a reported record-stream error: after it (and nmg_clear_buffers) the
+ * engine analyses other buffers as a new one would.  Per buffer counts
+ * replaced by nmg_set_buffer_counts are dropped (the engine's own buffers
+ * again). */
 int nmg_reset_counters(nmg_engine *h);
 /* Drop every submitted buffer (staging memory is kept for reuse). */
 int nmg_clear_buffers(nmg_engine *h);

@@ -4,7 +4,8 @@
 // analysis ("the build's bit-exact C++ CPU
 // restatement on all host cores"), used by bench.py's cpu_baseline leg and
 // checked against the single-threaded oracle (oracle/nmg_oracle.c) by
-// tests/test_cpu_mt.py.  It is never part of the product path.
+// tests/test_cpu_mt.py and, on irregular record streams,
+// tests/test_record_streams_host.py.  It is never part of the product path.
 //
 // Same semantics as the oracle, with the reference's cost-shaping structures
 // replaced by flat ones so that it runs at configs[2]-[3] sizes:
@@ -160,22 +161,23 @@ int load(const char* path, Table& t, std::vector<Buffer>& bufs) {
     t.ent[e] = Entry{rd64(q), rd64(q + 8), rd64(q + 24), rd64(q + 32)};
   }
   off += 72ull * t.nb_entries + 8 * cs_len + ((str_len + 7) & ~7ull);
-  bufs.resize(nb);
+  bufs.reserve(nb);
   for (uint32_t b = 0; b < nb; b++) {
-    Buffer& B = bufs[b];
+    Buffer B;
     B.thread_rank = rd32(p + off);
     B.access = rd32(p + off + 4);
     const uint64_t tail = rd64(p + off + 8), head = rd64(p + off + 16), ring = rd64(p + off + 24);
     off += 32;
     const uint8_t* r = p + off;
-    if (head == tail) {
-    } else if (head < tail) {  // two segments (mem_sampling.c:704-713)
+    off += (ring + 7) & ~7ull;
+    if (head == tail) continue;  // empty ring: never pushed (mem_sampling.c:680-682), no analysis index
+    if (head < tail) {  // two segments (mem_sampling.c:704-713)
       B.bytes.assign(r + tail, r + ring);
       B.bytes.insert(B.bytes.end(), r, r + head);
     } else {
       B.bytes.assign(r + tail, r + head);
     }
-    off += (ring + 7) & ~7ull;
+    bufs.push_back(std::move(B));
   }
   // fences and the dense page-cell layout (the engine's default 4 GiB budget)
   for (uint32_t k = 0; k < t.nb_keys; k += kFenceStep) t.fences.push_back(t.keys[k]);

@@ -267,7 +267,12 @@ def _one_buffer_replay(raw_bytes):
 def test_error_codes(tmp_path, case, code):
     """Malformed records: the reference abort()s (size 0, mem_sampling.c:857)
     or reads out of bounds (truncated SAMPLE, :865-879); the engine returns
-    the matching NMG_ERR_* code instead."""
+    the matching NMG_ERR_* code instead.  (One buffer of 20 records over 10
+    intervals: attribute_kernel's first window only.  The matrix of kinds,
+    positions and paths, with the reported buffer and byte offset, the route
+    pass's error reporting and several malformed buffers at once are
+    test_gpu_record_streams.py's test_error_matrix and
+    test_first_error_in_analysis_order.)"""
     from numamma_amd.engine import Engine
 
     rec = np.zeros(20, dtype=RECORD_DTYPE)
