@@ -592,8 +592,9 @@ int nmg_report_page_cost_host(const struct nmg_host_results *res, const struct n
  * A group is one object (nmg_*_object_blocks; group = entry id, R = its
  * pages) or one call site (nmg_report_placement; group = site id, members =
  * the site's objects, R = the rows of its callsite_counters_<id>.dat, a
- * member's pages past R dropped).  Only entries with dense page cells
- * contribute (huge ranges such as [stack] do not: the timeline's selection).
+ * member's pages past R dropped).  Without NMG_PLACE_HUGE only entries with
+ * dense page cells contribute (huge ranges such as [stack] do not: the
+ * timeline's selection); with it every member entry contributes (below).
  * For page p < R and node n:
  *   c[p][n] = sum over the members e with p < pages(e) and the threads t with
  *             thread_node[t] == n of the page cell (e, t, p)      (u64 sums)
@@ -635,13 +636,16 @@ int nmg_report_page_cost_host(const struct nmg_host_results *res, const struct n
  *
  * Errors: NMG_ERR_INVALID for a NULL argument, nb_nodes outside 1..64, a
  * thread_node value >= nb_nodes, a NULL thread_node with nb_threads not a
- * multiple of nb_nodes, a source other than the two below (and the cost
- * source for nmg_report_placement_host: nmg_host_results has no cost rows), or
+ * multiple of nb_nodes, a source other than the three below -- among them
+ * NMG_PLACE_PAGE_COST | NMG_PLACE_HUGE: sparse entries have no cost cells,
+ * which the error detail says -- (and the cost source for
+ * nmg_report_placement_host: nmg_host_results has no cost rows), or
  * an engine without NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST; NMG_ERR_STATE before
  * nmg_set_objects, and for NMG_PLACE_PAGE_COST with no cost cells set;
  * NMG_ERR_IO when blocks.dat cannot be written.  Multi-GPU
  * handles, streamed and online engines are accepted: the rule reads the
- * (merged) histogram only.  The object blocks are cached per results epoch
+ * (merged) histogram and, with NMG_PLACE_HUGE, the handle's sparse cells
+ * only.  The object blocks are cached per results epoch
  * and options: nmg_count_object_blocks then nmg_get_object_blocks computes
  * once.  nmg_report_placement gives its sites the ids nmg_report gives them
  * (opts->online as there); nmg_report_placement_host computes the same file
@@ -654,15 +658,35 @@ int nmg_report_page_cost_host(const struct nmg_host_results *res, const struct n
  * place: "the page cell (e, t, p)" is then the cost cell, cnt and the rows'
  * count are cost sums, and density_threshold is compared with them.  The
  * rule, the rows and blocks.dat are otherwise the same.  The cached object
- * blocks are keyed by the source too. */
+ * blocks are keyed by the source too.
+ *
+ * NMG_PLACE_HUGE (a flag bit, with NMG_PLACE_PAGE_COUNTS only): every member
+ * entry contributes, the sparse ones included -- entries of more than 2^24
+ * page cells over all threads, such as [stack] or a multi-GiB array, and the
+ * entries that the histogram budget (hist_budget_bytes) left without dense
+ * cells.  A dense entry contributes through its histogram cells; a sparse
+ * entry through the sparse cells (nmg_get_page_cells returns both kinds):
+ * "the page cell (e, t, p)" of a sparse entry is the count kept under its
+ * sparse index, t and p.  A page number is that key's 32-bit page field:
+ * pages(e) and R are taken as at most 2^32 - 1.  The rule, the rows, their
+ * order and blocks.dat are otherwise the same, and an engine without sparse
+ * entries gives the rows it gives without the flag.  A group with a sparse
+ * member is computed from its touched pages alone, on the device
+ * (nmg_*_object_blocks, nmg_report_placement) and on the host
+ * (nmg_report_placement_host, where an entry counts as sparse by the
+ * per-entry cap above and every entry of res->cells contributes): neither
+ * allocates per page of such a group.  The cached object blocks are keyed by
+ * the flag too. */
 #define NMG_PLACE_PAGE_COUNTS 0
 #define NMG_PLACE_PAGE_COST 2
+#define NMG_PLACE_HUGE 4 /* every entry contributes, sparse cells included */
 struct nmg_placement_options {
   uint32_t nb_nodes;            /* 1..64 */
   uint32_t density_threshold;   /* a page qualifies when its dominant node's count > this; the script's value is 8 */
   const uint32_t *thread_node;  /* [nb_threads], each < nb_nodes; NULL: rank / (nb_threads / nb_nodes),
                                    nb_threads % nb_nodes == 0 */
-  uint64_t source;              /* NMG_PLACE_PAGE_COUNTS / NMG_PLACE_PAGE_COST; any other value is refused */
+  uint64_t source;              /* NMG_PLACE_PAGE_COUNTS (| NMG_PLACE_HUGE) / NMG_PLACE_PAGE_COST; any other value
+                                   is refused */
 };
 int64_t nmg_count_object_blocks(nmg_engine *h, const struct nmg_placement_options *p);
 int nmg_get_object_blocks(nmg_engine *h, const struct nmg_placement_options *p, uint64_t *rows /* [n][5] */, int64_t n);
@@ -673,8 +697,9 @@ int nmg_report_placement_host(const struct nmg_host_results *res, const struct n
 
 /* Convenience driver used by the nmg_replay CLI and the tests: load a replay
  * file (DESIGN.md "Replay format"), analyse it on `device`, report.
- * Environment: NMG_REPLAY_PLACEMENT=nb_nodes[:threshold] also writes
- * blocks.dat (nmg_report_placement, the NULL thread map, threshold 8). */
+ * Environment: NMG_REPLAY_PLACEMENT=nb_nodes[:threshold[:huge]] also writes
+ * blocks.dat (nmg_report_placement, the NULL thread map, threshold 8; the
+ * literal word "huge" as the third field sets NMG_PLACE_HUGE). */
 int nmg_run_replay(const char *replay_path, const char *output_dir, const char *stdout_path,
                    const char *raw_path, int device, uint32_t flags);
 

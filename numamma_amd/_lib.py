@@ -163,13 +163,14 @@ NMG_COST_NA = 0x40000
 NMG_COST_REMOTE = (1 << 5) | (1 << 6)
 NMG_COST_MEMORY = (1 << 4) | NMG_COST_REMOTE
 NMG_PLACE_PAGE_COUNTS, NMG_PLACE_PAGE_COST = 0, 2
+NMG_PLACE_HUGE = 4  # flag bit beside NMG_PLACE_PAGE_COUNTS: every entry contributes, sparse cells included
 
 
 def placement_options(nb_threads, nb_nodes, thread_node=None, density_threshold=8, reserved=0, source=0):
     """(nmg_placement_options, the array it points into): thread_node None is
     the NULL map, rank / (nb_threads / nb_nodes); otherwise one node per thread
     rank (the library reads nb_threads entries).  source: NMG_PLACE_PAGE_COUNTS
-    or NMG_PLACE_PAGE_COST; reserved= is the field's earlier name and sets the
+    (with or without NMG_PLACE_HUGE) or NMG_PLACE_PAGE_COST; reserved= is the field's earlier name and sets the
     same word."""
     import numpy as np
 

@@ -290,13 +290,23 @@ struct PlaceDev {
   uint64_t pages = 0;
   DevBuf<uint32_t> gid, m_off, m_np;
   DevBuf<uint64_t> pg_off, m_base;
+  // NMG_PLACE_HUGE: the H groups with a sparse member (PlaceHugeParams' arrays)
+  uint32_t H = 0, DM = 0, nsent = 0;
+  uint64_t dcells = 0;
+  DevBuf<uint32_t> h_group, s_rank, s_lim, dm_rank;
+  DevBuf<uint64_t> dm_off, dm_base;
 };
 struct PlaceState {
   bool obj_dirty = true;  // hist_base / npages changed: the object groups are built and uploaded again
+  bool obj_huge = false;  // the object groups were built with NMG_PLACE_HUGE
   PlaceDev obj;
   DevBuf<uint32_t> d_thr, d_noff, d_bcnt;
   DevBuf<uint64_t> d_pvcnt, d_boff, d_part;
   DevBuf<uint8_t> d_pvnode;
+  // the huge groups' work arrays (run_huge)
+  DevBuf<uint32_t> d_tnode, d_hflag, d_hpnode, d_hlnode;
+  DevBuf<uint64_t> d_hkeys, d_hvals, d_hskeys, d_hsvals, d_hpcnt, d_hoff, d_hpart, d_hgfirst, d_hn;
+  DevBuf<uint8_t> d_htmp;
   // nmg_count_object_blocks, then the copy out: rows of this epoch and these options
   DevBuf<uint64_t> d_rows;
   uint64_t rows_epoch = 0;

@@ -1,6 +1,7 @@
 // nmg_internal.h -- engine internals shared by the HIP engine, the host report
 // writer and the replay driver.  Not part of the C-ABI.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -174,25 +175,34 @@ struct PlaceMap {
 int placement_map(const nmg_placement_options* p, uint32_t T, PlaceMap& out);
 // Groups in ascending gid order, group g's members at [m_off[g], m_off[g + 1]).
 // rows[g] = min(R, the longest member): the pages past every member count
-// nothing and never qualify.  Groups without a dense member or a row are left out.
+// nothing and never qualify.  Groups without a dense member or a row are left
+// out.  all (NMG_PLACE_HUGE): the sparse entries are members too, and a group
+// that has one is huge[g]: it gets no per-page array, on the device or on the
+// host, and is walked over its members' cells instead.
+constexpr uint64_t kPlaceMaxPages = 0xffffffffull;  // a page number is the sparse key's 32-bit page field
 struct PlaceGroups {
   std::vector<uint32_t> gid, rows, m_off{0};
   std::vector<uint32_t> m_entry, m_np;  // member: its entry (report position), pages clipped to R
+  std::vector<uint8_t> huge;            // [groups] the group has a sparse member
+  std::vector<uint8_t> m_dense;         // [members]
   void add(uint32_t id, uint64_t R, const std::vector<uint32_t>& entries, const uint64_t* npages,
-           const uint8_t* dense);
+           const uint8_t* dense, bool all = false);
+  bool any_huge() const { return std::find(huge.begin(), huge.end(), 1) != huge.end(); }
 };
 struct PlaceSite {  // a call site that may get blocks
   uint32_t id;
   std::string caller, ident;
   uint64_t size;
 };
-// every entry with dense cells its own group
-void placement_object_groups(uint32_t E, const uint64_t* npages, const uint8_t* dense, PlaceGroups& g);
+// every entry with dense cells (all: every entry) its own group
+void placement_object_groups(uint32_t E, const uint64_t* npages, const uint8_t* dense, PlaceGroups& g,
+                             bool all = false);
 // the call sites of r (nmg_report's ids) that blocks.dat may list, one group each
 int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta, bool online,
                           const uint64_t* npages, const uint8_t* dense, PlaceGroups& g,
-                          std::vector<PlaceSite>& sites, std::string& err);
+                          std::vector<PlaceSite>& sites, std::string& err, bool all = false);
 // the rule on the host, from (entry, thread, page, count) cells sorted by entry: [n][5] rows appended
+// (a huge group from its members' cells alone: memory follows the cells, not the group's pages)
 void placement_blocks_host(const PlaceGroups& g, const PlaceMap& m, const uint32_t* cells, int64_t nb_cells,
                            uint32_t nb_entries, std::vector<uint64_t>& rows);
 // blocks.dat from the sites (ascending id) and their rows (group = site id)

@@ -304,7 +304,7 @@ struct PlaceParams {
   const uint32_t* node_off;  // [N + 1] node n's ranks at thr[node_off[n] .. node_off[n + 1])
   uint32_t N, D, G;
   const uint32_t* gid;      // [G] ascending
-  const uint64_t* pg_off;   // [G + 1] strictly ascending (every group has a row)
+  const uint64_t* pg_off;   // [G + 1] ascending; a group without pages here is a huge one (below)
   const uint32_t* m_off;    // [G + 1] group g's members [m_off[g], m_off[g + 1])
   const uint64_t* m_base;   // [M] member's first cell
   const uint32_t* m_np;     // [M] member's pages (<= the group's rows)
@@ -318,5 +318,62 @@ constexpr uint32_t kPlaceNoNode = 0xff;
 hipError_t launch_place_fold(hipStream_t s, const PlaceParams& p, uint64_t pages);
 hipError_t launch_place_count(hipStream_t s, const PlaceParams& p);
 hipError_t launch_place_emit(hipStream_t s, const PlaceParams& p);
+
+// NMG_PLACE_HUGE: the groups that have a sparse member ("huge": rank 0..H-1 in
+// group order) are computed from their touched pages alone.  Extract appends
+// one (key, count) item per non-zero cell of their members, key = rank << 38 |
+// page << 6 | node; the items are sorted by key; reduce gives every (rank,
+// page) head item the page's cnt and dom; the qualifying pages are compacted
+// into a list in (rank, page) order; a list item whose rank or node differs
+// from the item before it starts a block.  The blocks per group go into
+// PlaceParams::bcnt beside the dense groups', so that one scan places both
+// kinds' rows in one array.
+constexpr uint32_t kPlaceRankShift = 38, kPlaceNodeBits = 6;
+struct PlaceHugeParams {
+  // the sparse table and the sparse entries of the current table
+  const uint64_t* sparse_keys;
+  const uint32_t* sparse_vals;
+  uint64_t sparse_cap;
+  uint32_t nsent;           // sparse indices
+  const uint32_t* s_rank;   // [nsent] the huge group of the entry, ~0: none (not a member, or no longer sparse)
+  const uint32_t* s_lim;    // [nsent] the member's pages
+  // the dense members of huge groups: member d's cells [dm_off[d], dm_off[d + 1]) of dcells per thread
+  const uint32_t* hist;
+  uint64_t hist_cells;
+  uint32_t DM;
+  uint64_t dcells;
+  const uint64_t* dm_off;   // [DM + 1]
+  const uint64_t* dm_base;  // [DM] first histogram cell
+  const uint32_t* dm_rank;  // [DM]
+  const uint32_t* tnode;    // [T] thread rank -> node
+  uint32_t T, D, H;
+  const uint32_t* h_group;  // [H] rank -> group index (PlaceParams' arrays)
+  const uint32_t* gid;      // [G]
+  // items: cap of them at most, *n_items appended
+  unsigned long long* n_items;
+  uint64_t cap;
+  uint64_t* keys;           // extract's output; after the sort the list's (rank << 32 | page)
+  uint64_t* vals;           // ... and the list's cnt
+  const uint64_t* skeys;    // [n] sorted
+  const uint64_t* svals;
+  uint64_t* pcnt;           // [n] head items: cnt(p)
+  uint32_t* pnode;          // [n] head items: dom(p)
+  uint32_t* flag;           // [n] 1: a head item whose page qualifies; later [m] 1: the list item starts a block
+  const uint64_t* off;      // [n + 1] / [m + 1] exclusive scan of flag
+  uint32_t* lnode;          // [m] the list's nodes
+  uint64_t* gfirst;         // [H] the first block (over all huge groups) of the group
+  uint32_t* bcnt;           // PlaceParams::bcnt
+  const uint64_t* boff;     // PlaceParams::boff
+  uint64_t* rows;           // PlaceParams::rows
+};
+hipError_t launch_place_huge_extract(hipStream_t s, const PlaceHugeParams& p, bool sparse);
+// the n items of keys / vals sorted by key into skeys / svals (tmp: tmp_bytes of workspace)
+size_t place_huge_sort_bytes(uint64_t n);
+hipError_t launch_place_huge_sort(hipStream_t s, const PlaceHugeParams& p, uint64_t n, void* tmp, size_t tmp_bytes);
+hipError_t launch_place_huge_reduce(hipStream_t s, const PlaceHugeParams& p, uint64_t n);
+hipError_t launch_place_huge_compact(hipStream_t s, const PlaceHugeParams& p, uint64_t n);
+hipError_t launch_place_huge_starts(hipStream_t s, const PlaceHugeParams& p, uint64_t m);
+hipError_t launch_place_huge_count(hipStream_t s, const PlaceHugeParams& p, uint64_t m);
+hipError_t launch_place_huge_emit(hipStream_t s, const PlaceHugeParams& p, uint64_t m);
 
 }  // namespace nmg

@@ -364,14 +364,18 @@ extern "C" int nmg_run_replay(const char* replay_path, const char* output_dir, c
   ro.nb_modules = (uint32_t)r.modules.size();
   rc = nmg_report(h, r.meta.data(), &ro, stdout_path);
   if (rc) return bail(rc);
-  // NMG_REPLAY_PLACEMENT=nb_nodes[:threshold]: blocks.dat after the report
-  // (the NULL thread map; threshold 8 as scripts/counters_to_binding.py)
+  // NMG_REPLAY_PLACEMENT=nb_nodes[:threshold[:huge]]: blocks.dat after the
+  // report (the NULL thread map; threshold 8 as scripts/counters_to_binding.py;
+  // "huge": NMG_PLACE_HUGE)
   const char* place = getenv("NMG_REPLAY_PLACEMENT");
   if (place && *place) {
     unsigned nodes = 0, thr = 8;
-    sscanf(place, "%u:%u", &nodes, &thr);
+    char word[8] = "";
+    const int nf = sscanf(place, "%u:%u:%7s", &nodes, &thr, word);
     nmg_placement_options po;
     memset(&po, 0, sizeof(po));
+    if (nf == 3 && !strcmp(word, "huge")) po.source = NMG_PLACE_PAGE_COUNTS | NMG_PLACE_HUGE;
+    else if (nf == 3) nodes = 0;  // (an unknown third field: refused with the options)
     po.nb_nodes = nodes;
     po.density_threshold = thr;
     rc = nmg_report_placement(h, r.meta.data(), &ro, &po);

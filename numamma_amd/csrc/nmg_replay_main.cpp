@@ -2,7 +2,7 @@
 //   nmg_replay replay.bin outdir [--raw raw.bin] [--device N] [--no-match]
 // Environment: NMG_REPLAY_DUMP=<NMG_DUMP_* flags> (the -d / -D / -u outputs,
 // with the replay's context section), NMG_REPLAY_STREAM=chunk[:threads[:batch]],
-// NMG_REPLAY_PLACEMENT=nb_nodes[:threshold] (blocks.dat, nmg_report_placement).
+// NMG_REPLAY_PLACEMENT=nb_nodes[:threshold[:huge]] (blocks.dat, nmg_report_placement).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,7 +14,7 @@ int main(int argc, char** argv) {
     fprintf(stderr,
             "usage: %s replay.bin outdir [--raw raw.bin] [--device N] [--no-match]\n"
             "  env NMG_REPLAY_DUMP=<1 -d | 2 -D | 4 -u>, NMG_REPLAY_STREAM=chunk[:threads[:batch]],\n"
-            "      NMG_REPLAY_PLACEMENT=nb_nodes[:threshold] (blocks.dat for libnuma_run.so's custom mbind policy)\n",
+            "      NMG_REPLAY_PLACEMENT=nb_nodes[:threshold[:huge]] (blocks.dat for libnuma_run.so's custom mbind policy)\n",
             argv[0]);
     return 2;
   }

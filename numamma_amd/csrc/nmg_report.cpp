@@ -576,8 +576,10 @@ int write_page_cost(const nmg_host_results* r, const nmg_object_meta* meta, cons
 // scripts/counters_to_binding.py are in include/numamma_gpu.h)
 
 int placement_map(const nmg_placement_options* p, uint32_t T, PlaceMap& out) {
+  // (NMG_PLACE_PAGE_COST | NMG_PLACE_HUGE: sparse entries have no cost cells)
   if (!p || p->nb_nodes < 1 || p->nb_nodes > 64 ||
-      (p->source != NMG_PLACE_PAGE_COUNTS && p->source != NMG_PLACE_PAGE_COST))
+      (p->source != NMG_PLACE_PAGE_COUNTS && p->source != NMG_PLACE_PAGE_COST &&
+       p->source != (NMG_PLACE_PAGE_COUNTS | NMG_PLACE_HUGE)))
     return NMG_ERR_INVALID;
   const uint32_t N = p->nb_nodes;
   if (!p->thread_node && T % N) return NMG_ERR_INVALID;
@@ -599,34 +601,39 @@ int placement_map(const nmg_placement_options* p, uint32_t T, PlaceMap& out) {
 }
 
 void PlaceGroups::add(uint32_t id, uint64_t R, const std::vector<uint32_t>& entries, const uint64_t* npages,
-                      const uint8_t* dense) {
+                      const uint8_t* dense, bool all) {
   const size_t m0 = m_entry.size();
   uint32_t longest = 0;
+  bool sparse = false;
   for (uint32_t e : entries) {
-    if (!dense[e]) continue;
-    const uint32_t np = (uint32_t)std::min<uint64_t>(npages[e], R);  // (dense: pages * threads <= 2^24)
+    if (!dense[e] && !all) continue;
+    // (dense: pages * threads <= 2^24; sparse: the key's 32-bit page field)
+    const uint32_t np = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(npages[e], R), kPlaceMaxPages);
     if (!np) continue;
     m_entry.push_back(e);
     m_np.push_back(np);
+    m_dense.push_back(dense[e] != 0);
+    sparse |= !dense[e];
     longest = std::max(longest, np);
   }
   if (m_entry.size() == m0) return;
   gid.push_back(id);
   rows.push_back(longest);
+  huge.push_back(sparse);
   m_off.push_back((uint32_t)m_entry.size());
 }
 
-void placement_object_groups(uint32_t E, const uint64_t* npages, const uint8_t* dense, PlaceGroups& g) {
+void placement_object_groups(uint32_t E, const uint64_t* npages, const uint8_t* dense, PlaceGroups& g, bool all) {
   std::vector<uint32_t> one(1);
   for (uint32_t e = 0; e < E; e++) {
     one[0] = e;
-    g.add(e, npages[e], one, npages, dense);
+    g.add(e, npages[e], one, npages, dense, all);
   }
 }
 
 int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta, bool online,
                           const uint64_t* npages, const uint8_t* dense, PlaceGroups& g,
-                          std::vector<PlaceSite>& sites, std::string& err) {
+                          std::vector<PlaceSite>& sites, std::string& err, bool all) {
   Registry reg(meta);
   if (r->match_samples) {
     const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
@@ -644,7 +651,7 @@ int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta
       continue;
     }
     const size_t g0 = g.gid.size();
-    g.add(s.id, s.mem_info_buffer_size / kPageSize + 1, s.objects, npages, dense);
+    g.add(s.id, s.mem_info_buffer_size / kPageSize + 1, s.objects, npages, dense, all);
     if (g.gid.size() != g0) sites.push_back(PlaceSite{s.id, s.caller, ident, s.buffer_size});
   }
   return NMG_OK;
@@ -666,8 +673,46 @@ void placement_blocks_host(const PlaceGroups& g, const PlaceMap& m, const uint32
   for (int64_t i = 0; i < nb_cells; i++) cell_begin[cells[4 * i] + 1]++;
   for (uint32_t e = 0; e < nb_entries; e++) cell_begin[e + 1] += cell_begin[e];
   std::vector<uint64_t> c;
+  std::vector<std::pair<uint64_t, uint64_t>> list;  // a huge group's cells: (page << 6 | node, count)
   for (size_t gi = 0; gi < g.gid.size(); gi++) {
     const uint32_t R = g.rows[gi];
+    if (g.huge[gi]) {
+      // the touched pages only: the members' cells gathered, sorted by (page,
+      // node), equal keys summed, then the walk below over the pages present
+      list.clear();
+      for (uint32_t k = g.m_off[gi]; k < g.m_off[gi + 1]; k++) {
+        const uint32_t e = g.m_entry[k], np = g.m_np[k];
+        for (int64_t i = cell_begin[e]; i < cell_begin[e + 1]; i++) {
+          const uint32_t* q = cells + 4 * i;
+          if (q[2] < np && q[1] < T && q[3]) list.push_back({(uint64_t(q[2]) << 6) | m.node[q[1]], q[3]});
+        }
+      }
+      std::sort(list.begin(), list.end());
+      bool open = false;
+      uint32_t prev = 0;
+      for (size_t i = 0; i < list.size();) {
+        const uint64_t page = list[i].first >> 6;
+        uint64_t best = 0;
+        uint32_t node = 0;
+        while (i < list.size() && list[i].first >> 6 == page) {
+          const uint64_t key = list[i].first;
+          uint64_t sum = 0;
+          for (; i < list.size() && list[i].first == key; i++) sum += list[i].second;
+          if (sum > best) best = sum, node = (uint32_t)(key & 63);  // (nodes ascending; strict: the lowest on a tie)
+        }
+        if (best <= m.D) continue;
+        if (!open || node != prev) {
+          const uint64_t row[5] = {g.gid[gi], node, page, page, best};
+          rows.insert(rows.end(), row, row + 5);
+          open = true;
+          prev = node;
+        } else {
+          rows[rows.size() - 2] = page;
+          rows[rows.size() - 1] += best;
+        }
+      }
+      continue;
+    }
     c.assign((size_t)R * U, 0);
     for (uint32_t k = g.m_off[gi]; k < g.m_off[gi + 1]; k++) {
       const uint32_t e = g.m_entry[k], np = g.m_np[k];
@@ -1073,12 +1118,14 @@ extern "C" int nmg_report_page_cost_host(const nmg_host_results* res, const nmg_
 
 namespace {
 // the host's view of the page cells: an entry's pages, and whether the engine
-// keeps them dense (CellCursor::place's per-entry cap; budgets aside)
+// keeps them dense (CellCursor::place's per-entry cap; budgets aside).  With
+// NMG_PLACE_HUGE the cap only chooses how a group is walked: every entry of
+// res->cells contributes.
 bool placement_host_args(const nmg_host_results* res, const nmg_placement_options* p, nmg::PlaceMap& map,
                          std::vector<uint64_t>& npages, std::vector<uint8_t>& dense) {
   if (!res || (res->nb_entries && !res->buffer_size) || (res->nb_cells && !res->cells) || res->nb_cells < 0 ||
       res->nb_threads > NMG_MAX_THREADS || nmg::placement_map(p, res->nb_threads, map) ||
-      p->source != NMG_PLACE_PAGE_COUNTS)  // (nmg_host_results has no cost rows)
+      (p->source & ~(uint64_t)NMG_PLACE_HUGE) != NMG_PLACE_PAGE_COUNTS)  // (nmg_host_results has no cost rows)
     return false;
   for (int64_t i = 0; i < res->nb_cells; i++)
     if (res->cells[4 * i] >= res->nb_entries || (i && res->cells[4 * i] < res->cells[4 * i - 4])) return false;
@@ -1104,7 +1151,8 @@ extern "C" int nmg_report_placement_host(const nmg_host_results* res, const nmg_
   nmg::PlaceGroups g;
   std::vector<nmg::PlaceSite> sites;
   std::vector<uint64_t> rows;
-  int rc = nmg::placement_site_groups(res, meta, opts && opts->online, npages.data(), dense.data(), g, sites, err);
+  int rc = nmg::placement_site_groups(res, meta, opts && opts->online, npages.data(), dense.data(), g, sites, err,
+                                      (p->source & NMG_PLACE_HUGE) != 0);
   if (!rc) {
     nmg::placement_blocks_host(g, map, res->cells, res->nb_cells, res->nb_entries, rows);
     rc = nmg::write_blocks(sites, rows.data(), (int64_t)(rows.size() / 5), opts, err);
@@ -1124,7 +1172,7 @@ extern "C" int64_t nmg_debug_object_blocks_host(const nmg_host_results* res, con
   std::vector<uint8_t> dense;
   if (!placement_host_args(res, p, map, npages, dense) || cap < 0 || (cap && !rows)) return NMG_ERR_INVALID;
   nmg::PlaceGroups g;
-  nmg::placement_object_groups(res->nb_entries, npages.data(), dense.data(), g);
+  nmg::placement_object_groups(res->nb_entries, npages.data(), dense.data(), g, (p->source & NMG_PLACE_HUGE) != 0);
   std::vector<uint64_t> out;
   nmg::placement_blocks_host(g, map, res->cells, res->nb_cells, res->nb_entries, out);
   const int64_t n = (int64_t)(out.size() / 5);

@@ -371,7 +371,9 @@ class Engine:
         thread_node[rank] is the node of a thread (None: rank / (nb_threads /
         nb_nodes)); a page counts when its dominant node has more than
         density_threshold accesses.  source = NMG_PLACE_PAGE_COST folds the
-        page cost cells (set_page_cost) instead of the counts."""
+        page cost cells (set_page_cost) instead of the counts; source =
+        NMG_PLACE_HUGE: every object, the ones with sparse page cells
+        ([stack], arrays past the dense cap or the histogram budget) included."""
         po, keep = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold, source=source)
         n = lib.nmg_count_object_blocks(self.h, C.byref(po))
         self._c(n)

@@ -153,28 +153,29 @@ def report_page_cost_host(res: RawResults, table, output_dir: str, rows: np.ndar
 
 
 def report_placement_host(res: RawResults, table, output_dir: str, nb_nodes: int, thread_node=None,
-                          density_threshold: int = 8, online: bool = False) -> None:
+                          density_threshold: int = 8, online: bool = False, source: int = 0) -> None:
     """nmg_report_placement_host(): <output_dir>/blocks.dat from host arrays (no
-    GPU involved), the options as Engine.report_placement takes them."""
+    GPU involved), the options as Engine.report_placement takes them (source:
+    NMG_PLACE_PAGE_COUNTS, or with NMG_PLACE_HUGE)."""
     from . import _lib
     from .engine import build_meta
 
     hr, keep = _host_results(res, table, np.zeros(res.nb_buffers, dtype=np.uint64), True)
     meta, kmeta = build_meta(table)
     ro = _lib.nmg_report_options(output_dir.encode(), 1, 0, None, None, None, 0, int(online))
-    po, kmap = _lib.placement_options(res.nb_threads, nb_nodes, thread_node, density_threshold)
+    po, kmap = _lib.placement_options(res.nb_threads, nb_nodes, thread_node, density_threshold, source=source)
     _lib.check(_lib.lib.nmg_report_placement_host(C.byref(hr), meta, C.byref(ro), C.byref(po)))
     del keep, kmeta, kmap
 
 
 def object_blocks_host(res: RawResults, table, nb_nodes: int, thread_node=None,
-                       density_threshold: int = 8) -> np.ndarray:
+                       density_threshold: int = 8, source: int = 0) -> np.ndarray:
     """Engine.object_blocks' rows computed on the host from res.cells (internal:
     the library's host statement of the rule; tools/placement_timing.py)."""
     from . import _lib
 
     hr, keep = _host_results(res, table, np.zeros(res.nb_buffers, dtype=np.uint64), True)
-    po, kmap = _lib.placement_options(res.nb_threads, nb_nodes, thread_node, density_threshold)
+    po, kmap = _lib.placement_options(res.nb_threads, nb_nodes, thread_node, density_threshold, source=source)
     n = _lib.check(_lib.lib.nmg_debug_object_blocks_host(C.byref(hr), C.byref(po), None, 0))
     rows = np.empty((n, 5), dtype=np.uint64)
     _lib.check(_lib.lib.nmg_debug_object_blocks_host(C.byref(hr), C.byref(po),

@@ -11,6 +11,11 @@ Both are cached per results epoch, so before every run the epoch is bumped by
 importing the engine's own sum64 array unchanged (a device copy, not timed).
 One warm-up and 5 timed runs each; a run that exceeds --limit seconds ends the
 process (exit status 124).  The timed work reads nothing but the engine.
+--huge also times (c), (a) with NMG_PLACE_HUGE: every entry contributes, the
+sparse ones through the sparse table; --hist-budget-bytes / --sparse-capacity
+give the engine a page-histogram budget that leaves a share of the entries
+sparse (the default budget leaves [stack] alone).  --sets N repeats (a)'s
+warm-up and runs N times: the spread between sets of unchanged code.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -32,6 +37,11 @@ def main():
     ap.add_argument("--threshold", type=int, default=8)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--limit", type=float, default=120.0, help="seconds a single run may take")
+    ap.add_argument("--huge", action="store_true", help="also time the object blocks with NMG_PLACE_HUGE")
+    ap.add_argument("--hist-budget-bytes", type=int, default=0, help="nmg_options.hist_budget_bytes (0: the default)")
+    ap.add_argument("--sparse-capacity", type=int, default=0, help="nmg_options.sparse_capacity (0: the default)")
+    ap.add_argument("--sets", type=int, default=1, help="how often (a) is measured (warm-up + runs each)")
+    ap.add_argument("--skip-host", action="store_true", help="leave out (b)")
     args = ap.parse_args()
 
     import numpy as np
@@ -39,7 +49,16 @@ def main():
 
     import bench  # (the generator and the device-resident engine setup: bench.Workload)
     from numamma_amd import _lib
-    from numamma_amd.engine import table_objects
+    import numamma_amd.engine as engine_mod
+
+    if args.hist_budget_bytes or args.sparse_capacity:  # (bench.Workload builds its engine with the defaults)
+        class BudgetedEngine(engine_mod.Engine):
+            def __init__(self, *a, **kw):
+                kw.setdefault("hist_budget_bytes", args.hist_budget_bytes)
+                kw.setdefault("sparse_capacity", args.sparse_capacity)
+                super().__init__(*a, **kw)
+
+        engine_mod.Engine = BudgetedEngine
 
     w = bench.Workload(args.workload, 0, torch.device("cuda", 0), False)
     eng, rp = w.eng, w.rp
@@ -78,6 +97,9 @@ def main():
     def device_path():
         return eng.object_blocks(args.nodes, None, args.threshold)
 
+    def device_path_huge():
+        return eng.object_blocks(args.nodes, None, args.threshold, source=_lib.NMG_PLACE_HUGE)
+
     sizes = np.ascontiguousarray(rp.table.entries["buffer_size"], dtype=np.uint64)
     cap = [0]
 
@@ -95,9 +117,25 @@ def main():
         assert n <= cap[0]
         return rows[:n], cells.shape[0]
 
-    a, rows_a = timed(device_path)
+    sets = []
+    for _ in range(max(1, args.sets)):
+        a, rows_a = timed(device_path)
+        sets.append(a["median_ms"])
+    huge = None
+    if args.huge:
+        c, rows_c = timed(device_path_huge)
+        nsparse = int(eng.sparse_export()[0].shape[0])
+        po, keep = _lib.placement_options(T, args.nodes, None, args.threshold, source=_lib.NMG_PLACE_HUGE)
+        cap[0] = rows_c.shape[0] + 1
+        _, (rows_h, ncells) = limited(host_path)  # (the host rule with the flag: the rows to compare with)
+        huge = dict(c, rows=int(rows_c.shape[0]), bytes_d2h=int(rows_c.nbytes), sparse_cells=nsparse, cells=int(ncells),
+                    rows_equal_host=bool(rows_c.shape == rows_h.shape and np.array_equal(rows_c, rows_h)))
+        po, keep = _lib.placement_options(T, args.nodes, None, args.threshold)
     cap[0] = rows_a.shape[0] + 1
-    b, (rows_b, ncells) = timed(host_path)
+    if args.skip_host:
+        b, rows_b, ncells = {}, rows_a, 0
+    else:
+        b, (rows_b, ncells) = timed(host_path)
     ent = rp.table.entries
     pages = ent["buffer_size"].astype(np.uint64) // np.uint64(4096) + np.uint64(1)
     dense = pages * np.uint64(T) <= np.uint64(1 << 24)
@@ -113,7 +151,20 @@ def main():
                                 bytes_h2d_once_per_table=int(dense.sum()) * 28 + 12),
         "b_page_cells_then_host_rule": dict(b, rows=int(rows_b.shape[0]), cells=int(ncells), bytes_d2h=int(ncells) * 16),
         "rows_equal": bool(rows_a.shape == rows_b.shape and np.array_equal(rows_a, rows_b)),
+        "a_set_medians_ms": sets,
+        "hist_budget_bytes": args.hist_budget_bytes, "sparse_capacity": args.sparse_capacity,
     }
+    if huge is not None:
+        out["c_object_blocks_huge"] = huge
+        # the entries the budget leaves dense (CellCursor::place in id order)
+        budget_cells = (args.hist_budget_bytes or 4 << 30) // 4
+        used, nd = 0, 0
+        for n, ok in zip(pages.tolist(), dense.tolist()):
+            if ok and (used + n) * T <= budget_cells:
+                used += n
+                nd += 1
+        huge["dense_entries_in_budget"] = nd
+        huge["sparse_entries"] = int(rp.table.nb_entries) - nd
     del keep
     print(json.dumps(out), flush=True)
     eng.close()
