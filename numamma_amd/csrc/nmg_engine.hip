@@ -309,7 +309,7 @@ extern "C" int nmg_analyze(nmg_engine* h) {
   const uint32_t grid = attribution_grid(h, nb);
   if (route_eligible(h)) {
     if (nb && (resched || grid != h->sched_grid || !h->sched_route ||
-               h->route_sched_key != (h->rt.nparts | ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u)))) {
+               h->route_sched_key != route_key(h))) {
       rc = build_schedule(h, grid, false);
       if (rc) return rc;
     }
@@ -622,6 +622,23 @@ extern "C" int nmg_debug_route_count(nmg_engine* h, uint64_t* n) {
   if (!h || !n) return NMG_ERR_INVALID;
   *n = h->route_launches;
   for (nmg_engine* w : h->workers) *n += w->route_launches;
+  return NMG_OK;
+}
+
+// Internal (not in include/numamma_gpu.h): the chunk pool of the
+// partition-first path as the last schedule left it (tests, sizing): out[0] =
+// log2 of a piece's chunks, [1] = pieces, [2] = chunk ids of the last layout
+// with the skipped ones, [3] = the capacities it was asked for, [4] = bytes
+// of the pieces
+extern "C" int nmg_debug_route_pool(nmg_engine* h, uint64_t out[5]) {
+  if (!h || !out) return NMG_ERR_INVALID;
+  const RoutePool& rp = h->rpool;
+  out[0] = rp.K;
+  out[1] = rp.pieces.size();
+  out[2] = rp.ids;
+  out[3] = rp.asked;
+  out[4] = 0;
+  for (const auto& p : rp.pieces) out[4] += p.cap() * sizeof(uint4);
   return NMG_OK;
 }
 

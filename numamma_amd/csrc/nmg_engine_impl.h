@@ -36,6 +36,7 @@
 
 #include "nmg_buffer.h"
 #include "nmg_kernels.h"
+#include "nmg_pool_layout.h"
 #include "nmg_route.h"
 
 using namespace nmg;
@@ -145,10 +146,16 @@ struct RouteTable {
 // the per-analysis buffers of the partition-first path, sized together
 // (route_pool): chunks = d_cmeta.cap(), grid = d_used.cap()
 struct RoutePool {
-  DevBuf<uint4> d_rec16;  // chunk pool: [chunks][kChunk] (addr, ts) and X words
-  DevBuf<uint32_t> d_cmeta;
+  // chunk pool: (addr, ts) and X words of chunk id at pieces[id >> K][(id & (2^K - 1)) * kChunk ...]
+  // (nmg_pool_layout.h); d_pieces = the pieces' base pointers, uploaded when the pool is built
+  std::vector<DevBuf<uint4>> pieces;
+  DevBuf<uint4*> d_pieces;
+  uint4* pool0 = nullptr;  // the lowest piece
+  uint32_t K = 0;
+  uint64_t ids = 0, asked = 0;  // the last layout: chunk ids with the skipped ones, and the workgroups' capacities
+  DevBuf<uint32_t> d_cmeta;   // [chunks], and so cmatch and clist: dense over the padded id space
   DevBuf<unsigned long long> d_cmatch;
-  DevBuf<uint32_t> d_clist;
+  DevBuf<uint2> d_clist;      // per list entry: chunk id | fill, and the chunk's distance from pool0, in chunks
   DevBuf<uint4> d_items;
   DevBuf<uint32_t> d_chunk0;  // [grid + 1]
   DevBuf<uint32_t> d_used;    // [grid]
@@ -474,7 +481,7 @@ struct nmg_engine {
   uint32_t nrsegs = 0;
   RoutePool rpool;
   bool sched_route = false;       // d_sdescs / d_ranges hold the analysis-order schedule
-  uint32_t route_sched_key = 0;   // nparts (| tiny-pool switch) the pools were sized for
+  uint32_t route_sched_key = 0;   // what the pools were laid out for (route_key)
   bool route_pending = false;     // per-buffer match counts of the last route analysis not yet summed
   uint32_t route_grid = 0;
   XLayout route_xl{};
@@ -483,6 +490,13 @@ struct nmg_engine {
   DevBuf<uint64_t> d_dbg;
   size_t dbg_len = 0;
 };
+
+// what a schedule's workgroup pools depend on besides the buffers: nparts, the
+// pool switches and the piece size of the pool they were laid out in
+inline uint32_t route_key(const nmg_engine* h) {
+  return h->rt.nparts | (h->rpool.K << 16) | ((h->flags & kDbgTinyPieces) ? 0x40000000u : 0u) |
+         ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u);
+}
 
 #define HIP_TRY(h, expr)                                                        \
   do {                                                                          \

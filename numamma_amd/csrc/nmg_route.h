@@ -33,6 +33,7 @@
 #pragma once
 
 #include "nmg_kernels.h"
+#include "nmg_pool_layout.h"
 
 namespace nmg {
 
@@ -96,6 +97,8 @@ constexpr uint32_t kFoundLds = 16384;      // found_kernel: per-buffer LDS count
 constexpr uint32_t kDbgNoRoute = 0x10000;  // large tables: the single-pass attribute_kernel instead
 constexpr uint32_t kDbgTinyPool = 0x20000; // route pass: private pools of 2 chunks, so the pool-overflow
                                            // (direct attribution) path runs
+constexpr uint32_t kDbgTinyPieces = 0x200000;  // chunk pool: the smallest pieces that hold the largest workgroup pool,
+                                               // not kPieceLog2: small workloads span pieces and padding (tests)
 // ablation switches (tools/ablate.py; results are wrong with them)
 constexpr uint32_t kDbgTinyOvf = 0x80000;  // route pass: an overflow list of 64 records, the rest attributed directly
                                            // (tests, with kDbgTinyPool)
@@ -168,7 +171,8 @@ struct RouteParams {
   uint32_t nparts;
   XLayout xl;
   uint64_t seq0;             // analysis index of descriptor 0 (seq = seq0 + index)
-  uint4* rec16;              // [chunks][kChunk] compact records
+  uint4* const* pieces;      // chunk pool: compact records of chunk id at pieces[id >> pk][(id & (2^pk - 1)) * kChunk ...]
+  uint32_t pk;               // (nmg_pool_layout.h; a workgroup's range [chunk0[w], chunk0[w + 1]) lies in one piece)
   uint32_t* cmeta;           // [chunks] partition | fill << 24
   const uint32_t* chunk0;    // [grid + 1] private chunk range of each workgroup
   uint32_t* used;            // [grid] chunks taken
@@ -192,7 +196,11 @@ struct ScatterParams {
   const uint32_t* used;
   const uint32_t* pcnt;   // exclusive prefixes (plan_kernel)
   const uint32_t* pbase;
-  uint32_t* clist;        // [chunks] chunk id | fill << kChunkIdBits, grouped by partition
+  uint2* clist;           // [chunks] grouped by partition: x = chunk id | fill << kChunkIdBits, y = coff: the
+                          // chunk lies at pool0 + coff * kChunk records (one 8 B store per chunk)
+  uint4* const* pieces;   // chunk pool (RouteParams::pieces, ::pk)
+  uint64_t pool0;         // the lowest piece's address: every chunk lies less than 2^32 chunks above it
+  uint32_t pk;
   uint32_t nparts;
 };
 
@@ -210,9 +218,10 @@ struct LocalParams {
                              // nmg_update_objects), or null: the id is the position (nmg_set_objects)
   const uint32_t* pe_lrel;   // [table entries] an entry's first packed cell (PartInfo::cmap != ~0)
   const uint32_t* pe_cmap;   // packed cell -> histogram cell
-  const uint4* rec16;
+  const uint4* pool0;        // chunk pool: the lowest piece (ScatterParams::pool0)
   const uint32_t* cmeta;
-  const uint32_t* clist;     // chunk id | fill << kChunkIdBits, grouped by partition
+  const uint2* clist;        // (chunk id | fill << kChunkIdBits, the chunk's place above pool0 in chunks), grouped
+                             // by partition
   const uint4* items;
   uint32_t* ctl;             // [0] items, [1] dequeue head, [3] records of the overflow path (plan_kernel)
   unsigned long long* cmatch;  // [chunks] match bit per record
@@ -230,7 +239,8 @@ struct FoundParams {
   const uint32_t* used;
   const uint32_t* cmeta;
   const unsigned long long* cmatch;
-  const uint4* rec16;
+  uint4* const* pieces;      // chunk pool (RouteParams::pieces)
+  uint32_t pk;
   uint32_t* bufcnt;          // [2][nb_bufs]
   uint32_t nb_bufs, gbits, gshift;
 };

@@ -495,6 +495,23 @@ __device__ __forceinline__ void route2_advance(unsigned long long* st, uint32_t 
   }
 }
 
+// The chunk pool's pieces (nmg_pool_layout.h): chunk id lies in piece
+// id >> pk at chunk id & (2^pk - 1).
+// the pointer b with b[id * kChunk + slot] = slot `slot` of chunk id, for
+// every id of c's piece
+// (a pointer read from memory, unlike a kernel argument, is not known to be
+// global memory, and its loads and stores would be flat instructions: the
+// pool is read and written through pointers that say so)
+#define NMG_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t rec16_t __attribute__((ext_vector_type(4)));  // a compact record as a plain vector
+typedef NMG_GLOBAL rec16_t grec16_t;
+__device__ __forceinline__ rec16_t rec16_of(const uint4& v) { return rec16_t{v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ grec16_t* pool_piece(uint64_t base) { return (grec16_t*)base; }
+__device__ __forceinline__ grec16_t* pool_vbase(uint4* const* pieces, uint32_t pk, uint32_t c) {
+  const uint32_t pc = c >> pk;
+  return pool_piece(reinterpret_cast<uint64_t>(pieces[pc]) - ((uint64_t(pc) << pk) * kChunk) * sizeof(uint4));
+}
+
 // a claim's outcome: the rec16 slot (~0: none), its chunk line, the
 // overflow list; !ok: a void claim, past the next chunk -- wait for
 // generation waitg to end and claim again
@@ -581,6 +598,9 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
   const uint32_t c0 = rp.chunk0[blockIdx.x];
   const uint32_t cap = rp.chunk0[blockIdx.x + 1] - c0;
   const uint32_t capl = min(cap, kStMaxLocal + 1);  // (pool indices fit the state's 20-bit fields)
+  // the workgroup's chunks lie in one piece of the pool: rec16[global slot] is
+  // right for every chunk of [c0, c0 + cap) (a "virtual base", wave-uniform)
+  grec16_t* const rec16 = pool_vbase(rp.pieces, rp.pk, c0);
   for (uint32_t i = tid; i < kMaxParts + 1; i += kR2WG) s_pb[i] = rp.pbounds[i];
   for (uint32_t i = tid; i < kRouteDir; i += kR2WG) s_pdir[i] = rp.pdir[i];
   if (tid < (int)((kMaxParts + 1) / 32)) s_dead[tid] = rp.pdead[tid];
@@ -910,7 +930,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
             if (jj < nd) {
               const uint2 t = s_tab[wave][jj];
               const uint32_t tq = t.x & 2047u, tm = (t.x >> 11) & 15u, k = lane & 3;
-              if ((tm >> k) & 1) rp.rec16[uint64_t(t.y) * 4 + k] = s_line[tq * 4 + k];
+              if ((tm >> k) & 1) rec16[uint64_t(t.y) * 4 + k] = rec16_of(s_line[tq * 4 + k]);
               piece_done(t, k);
             }
           }
@@ -927,7 +947,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
       // too -- one store instruction for every record stored alone; nothing
       // reads the slots before the local pass)
       const bool alone = straight || (counts && !staged && dst != ~0ull);
-      if (alone) rp.rec16[dst] = X.a;
+      if (alone) rec16[dst] = rec16_of(X.a);
       if (TIMING) {  // (records staged / stored straight to their slot)
         rt.acc[6] += (uint64_t)__popcll(__ballot(staged));
         rt.acc[7] += (uint64_t)__popcll(__ballot(straight));
@@ -997,7 +1017,7 @@ __global__ __launch_bounds__(kR2WG, 1) void route2_kernel(RouteParams rp) {
     if (q < nlp) {
       const uint32_t m = lw_mask(s_lw[q]);
       for (uint32_t j = 0; j < 4; j++)
-        if ((m >> j) & 1u) rp.rec16[uint64_t(s_ldst[q]) * 4 + j] = s_line[q * 4 + j];
+        if ((m >> j) & 1u) rec16[uint64_t(s_ldst[q]) * 4 + j] = rec16_of(s_line[q * 4 + j]);
     }
   }
   if (tid == 0) rp.used[blockIdx.x] = min(s_taken, capl);
@@ -1153,6 +1173,11 @@ __global__ __launch_bounds__(kWG) void scatter_kernel(ScatterParams r) {
   for (uint32_t q = tid; q < P; q += kWG) s_cnt[q] = r.pbase[q] + off[q];
   __syncthreads();
   const uint32_t c0 = r.chunk0[w], n = r.used[w];
+  // where the workgroup's chunks lie, for the local pass: chunk id is chunk
+  // voff + id from pool0 (all in one piece; u32 arithmetic, wrapping)
+  const uint32_t pc = c0 >> r.pk;
+  const uint32_t voff =
+      (uint32_t)((reinterpret_cast<uint64_t>(r.pieces[pc]) - r.pool0) / (kChunk * sizeof(uint4))) - (pc << r.pk);
   constexpr uint32_t kU = 8;  // chunk tags in flight per thread
   for (uint32_t b = 0; b < n; b += kU * kWG) {
     uint32_t m[kU];
@@ -1165,7 +1190,8 @@ __global__ __launch_bounds__(kWG) void scatter_kernel(ScatterParams r) {
     for (uint32_t u = 0; u < kU; u++) {
       if (!(m[u] >> 24)) continue;
       const uint32_t k = atomicAdd(&s_cnt[m[u] & 0xffffffu], 1u);
-      r.clist[k] = (c0 + b + u * kWG + tid) | ((m[u] >> 24) << kChunkIdBits);  // chunk id | fill
+      const uint32_t id = c0 + b + u * kWG + tid;
+      r.clist[k] = make_uint2(id | ((m[u] >> 24) << kChunkIdBits), voff + id);  // chunk id | fill, its place
     }
   }
 }
@@ -1227,6 +1253,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   __shared__ uint32_t s_clist[kItemChunks];  // the item's chunk list entries
   __shared__ uint32_t s_item, s_cnext, s_nfound, s_big, s_took;
   __shared__ uint4 s_nx[4];  // the next item's work item and PartInfo (take_next)
+  __shared__ uint32_t s_coff[kItemChunks];  // and where each chunk lies (LocalParams::clist .y)
 
   Params& p = lp.p;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1292,7 +1319,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       uint64_t key = 0;
       uint4 pn = make_uint4(0, 0, 0, 0), od = pn;
       uint2 inf = make_uint2(0, 0);
-      uint32_t oi = 0, cl[kClPer];
+      uint32_t oi = 0, cl[kClPer], cf[kClPer];
       if (tid < nk) {
         key = lp.pe_keys[uint64_t(q) * kPartSlots + tid];
         pn = lp.pe_pnode[uint64_t(q) * kPartSlots + tid];
@@ -1304,7 +1331,11 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         oi = lp.pe_oinf[uint64_t(q) * kOldLds + tid];
       }
 #pragma unroll
-      for (uint32_t u = 0; u < kClPer; u++) cl[u] = tid + u * kLWG < ncl ? lp.clist[item.y + tid + u * kLWG] : 0u;
+      for (uint32_t u = 0; u < kClPer; u++) {
+        const uint2 ce = tid + u * kLWG < ncl ? lp.clist[item.y + tid + u * kLWG] : make_uint2(0u, 0u);
+        cl[u] = ce.x;
+        cf[u] = ce.y;
+      }
       if (tid < nk) {
         s_keys[tid] = key;
         s_pn[tid] = pn;
@@ -1317,7 +1348,10 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       }
 #pragma unroll
       for (uint32_t u = 0; u < kClPer; u++)
-        if (tid + u * kLWG < ncl) s_clist[tid + u * kLWG] = cl[u];
+        if (tid + u * kLWG < ncl) {
+          s_clist[tid + u * kLWG] = cl[u];
+          s_coff[tid + u * kLWG] = cf[u];
+        }
     }
     if (tid == 0) {
       s_cnext = 0;
@@ -1345,8 +1379,9 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     // end with vmcnt(0).
     const uint32_t nl = item.z - item.y;
     auto chunk_load = [&](uint32_t l, uint4& a) {  // the chunk at list position l (l >= nl: none; no branch)
-      const uint32_t e = l < nl ? s_clist[l] : 0u;
-      a = lp.rec16[uint64_t(e & ((1u << kChunkIdBits) - 1)) * kChunk + lane];
+      // (the chunk's place in the pool's pieces was resolved by scatter_kernel; none: the pool's lowest chunk)
+      const uint32_t e = l < nl ? s_coff[l] : 0u;
+      a = lp.pool0[uint64_t(e) * kChunk + lane];
     };
     // the kLC chunks at list positions l0, l0 + 1, ... (past the list: no valid lane)
     auto process = [&](uint32_t l0, const uint4 (&a16)[kLC]) {
@@ -1887,6 +1922,8 @@ __global__ __launch_bounds__(kWG) void found_kernel(FoundParams r) {
   __syncthreads();
   const uint64_t k0 = uint64_t(r.chunk0[w]) * kChunk, k1 = k0 + uint64_t(r.used[w]) * kChunk;
   const uint64_t gmask = (1ull << r.gbits) - 1;
+  // (the workgroup's chunks lie in one piece: as in route2_kernel)
+  const NMG_GLOBAL uint64_t* const xwords = (const NMG_GLOBAL uint64_t*)pool_vbase(r.pieces, r.pk, r.chunk0[w]);
   // one record per lane, a chunk per wave-instruction: the bit word is a
   // wave-uniform load, the X words stream (bits past a chunk's fill are 0)
   constexpr int kU = 4;
@@ -1898,7 +1935,7 @@ __global__ __launch_bounds__(kWG) void found_kernel(FoundParams r) {
       // (a chunk of fill 0 -- route2 opened it and nothing reached it -- was
       // never given to the local pass: its match bits are stale)
       bits[u] = kk < k1 && (r.cmeta[kk / kChunk] >> 24) ? r.cmatch[kk / kChunk] : 0ull;
-      xw[u] = ((bits[u] >> lane) & 1) ? reinterpret_cast<const uint64_t*>(r.rec16)[2 * kk + 1] >> r.gshift : 0ull;
+      xw[u] = ((bits[u] >> lane) & 1) ? xwords[2 * kk + 1] >> r.gshift : 0ull;
     }
 #pragma unroll
     for (int u = 0; u < kU; u++) {

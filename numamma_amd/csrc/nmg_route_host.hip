@@ -40,9 +40,11 @@ bool route_eligible(nmg_engine* h, const std::vector<BufDesc>& descs) {
     if (descs[i].seq != descs[0].seq + i) return false;
     bytes += descs[i].len;
   }
-  // chunk ids (route pass LDS: id << 7 | fill) -- an upper bound of the pool
+  // chunk ids (route pass LDS: id << 7 | fill) -- an upper bound of the pool,
+  // twice over: the ids skipped before a workgroup's range, so that it lies in
+  // one piece (pool_layout), are fewer than the range holds
   const uint64_t chunks = (bytes / kRecBytes + descs.size()) / kChunk + (uint64_t)h->num_cus * (2 * h->rt.nparts + 2);
-  if (chunks >= (1ull << kChunkIdBits)) return false;
+  if (2 * chunks >= (1ull << kChunkIdBits)) return false;
   XLayout xl;
   return route_layout(h, descs, xl);
 }
@@ -55,31 +57,79 @@ int route_pool(nmg_engine* h, const std::vector<BufDesc>& descs, uint32_t grid, 
                       std::vector<uint32_t>& c0) {
   const uint32_t P = h->rt.nparts;
   c0.assign(grid + 1, 0);
-  uint64_t tot = 0;
+  std::vector<uint64_t> caps(grid);
+  uint64_t maxcap = 1;
   for (uint32_t w = 0; w < grid; w++) {
     uint64_t rec = 0;
     for (uint32_t b = ranges[w]; b < ranges[w + 1]; b++) rec += (descs[b].len + kRecBytes - 1) / kRecBytes;
     // (route2_kernel keeps two chunks open per partition: the open one and
     // the next, opened ahead)
-    const uint64_t cap = (h->flags & kDbgTinyPool) ? 2 : (rec + kChunk - 1) / kChunk + 2 * P;
-    c0[w] = (uint32_t)tot;
-    tot += cap;
+    caps[w] = (h->flags & kDbgTinyPool) ? 2 : (rec + kChunk - 1) / kChunk + 2 * P;
+    maxcap = std::max(maxcap, caps[w]);
   }
-  c0[grid] = (uint32_t)tot;
-  if (tot >= (1ull << kChunkIdBits)) return fail(h, NMG_ERR_RANGE, "partition-first chunk pool too large");
-  const size_t items = tot / kItemChunks + P + 1;
+  // the workgroups' ranges in the pool's pieces (nmg_pool_layout.h): in the
+  // pieces the pool has if they serve, else in pieces of 2^kPieceLog2 chunks,
+  // larger where the largest range asks for it
+  RoutePool& rp = h->rpool;
+  const uint64_t limit = 1ull << kChunkIdBits;
+  const uint32_t Kmin = pool_min_log2(maxcap);
+  uint32_t K = rp.K, npieces = 0;
+  const bool fits = !rp.pieces.empty() && K >= Kmin &&
+                    pool_layout(caps.data(), grid, K, limit, c0.data(), &npieces) && npieces <= rp.pieces.size();
+  if (!fits) {
+    K = (h->flags & kDbgTinyPieces) ? Kmin : std::max(Kmin, kPieceLog2);
+    if (!pool_layout(caps.data(), grid, K, limit, c0.data(), &npieces))
+      return fail(h, NMG_ERR_RANGE, "partition-first chunk pool too large");
+  }
+  uint64_t tot = c0[grid];
+  size_t items = tot / kItemChunks + P + 1;
   // overflow list: records past a full pool (only SAMPLE records shorter than
   // 40 B can get there; kDbgTinyPool sends nearly all of them)
   uint64_t recs = 0;
   for (const BufDesc& d : descs) recs += (d.len + kRecBytes - 1) / kRecBytes;
   // (a quarter of the records, plus up to three times them for batches under 4M records)
   const size_t ovf = (size_t)((h->flags & kDbgTinyPool) ? recs : recs / 4 + std::min<uint64_t>(3 * recs, 4u << 20)) + 65536;
-  RoutePool& rp = h->rpool;
-  if (tot > rp.d_cmeta.cap() || items > rp.d_items.cap() || grid > rp.d_used.cap() || ovf > rp.d_ovfx.cap()) {
+  if (!fits || tot > rp.d_cmeta.cap() || items > rp.d_items.cap() || grid > rp.d_used.cap() || ovf > rp.d_ovfx.cap()) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // a launch in flight may still read the old pool
     rp = RoutePool();  // (the whole pool anew, sized together; route_pending is kept)
+    // the pieces, each a device allocation of its own.  The local pass finds a
+    // chunk by its distance from the lowest piece, a u32 of chunks
+    // (ScatterParams::clist .y): should the allocator ever spread the pieces
+    // further than that, the pool is one piece.
+    std::vector<uint4*> bases;
+    for (bool single = false;; single = true) {
+      if (single) {
+        uint64_t asked = 0;
+        for (uint64_t c : caps) asked += c;
+        K = pool_min_log2(std::max<uint64_t>(asked, 1));
+        if (!pool_layout(caps.data(), grid, K, limit, c0.data(), &npieces))
+          return fail(h, NMG_ERR_RANGE, "partition-first chunk pool too large");
+        tot = c0[grid];
+        items = tot / kItemChunks + P + 1;
+      }
+      npieces = std::max(npieces, 1u);
+      rp.pieces.clear();
+      rp.pieces.resize(npieces);
+      bases.assign(npieces + 1, nullptr);  // (one more, null: a range that starts where the ids end)
+      uintptr_t lo = ~uintptr_t(0), hi = 0, misaligned = 0;
+      for (uint32_t i = 0; i < npieces; i++) {
+        // (the last piece ends with the ids: d_cmeta.cap() bounds every later layout)
+        const size_t nch = i + 1 < npieces ? size_t(1) << K : std::max<size_t>(tot, 1) - (size_t(i) << K);
+        HIP_TRY(h, rp.pieces[i].alloc(nch * kChunk));
+        bases[i] = rp.pieces[i];
+        const uintptr_t b = reinterpret_cast<uintptr_t>(bases[i]);
+        lo = std::min(lo, b);
+        hi = std::max(hi, b + nch * kChunk * sizeof(uint4));
+        misaligned |= b % (kChunk * sizeof(uint4));
+      }
+      rp.pool0 = reinterpret_cast<uint4*>(lo);
+      if (!misaligned && (hi - lo) / (kChunk * sizeof(uint4)) < (1ull << 32)) break;
+      if (single) return fail(h, NMG_ERR_HIP, "partition-first chunk pool: unusable device allocation");
+    }
+    rp.K = K;
     const size_t cap = std::max<size_t>(tot, 1);
-    HIP_TRY(h, rp.d_rec16.alloc(cap * kChunk));
+    HIP_TRY(h, rp.d_pieces.alloc(npieces + 1));
+    HIP_TRY(h, hipMemcpy(rp.d_pieces, bases.data(), (npieces + 1) * sizeof(uint4*), hipMemcpyHostToDevice));
     HIP_TRY(h, rp.d_cmeta.alloc(cap));
     HIP_TRY(h, rp.d_cmatch.alloc(cap));
     HIP_TRY(h, rp.d_clist.alloc(cap));
@@ -93,6 +143,9 @@ int route_pool(nmg_engine* h, const std::vector<BufDesc>& descs, uint32_t grid, 
     HIP_TRY(h, rp.d_ovf16.alloc(ovf));
     HIP_TRY(h, rp.d_ovfx.alloc(ovf));
   }
+  rp.ids = tot;
+  rp.asked = 0;
+  for (uint64_t c : caps) rp.asked += c;
   return NMG_OK;
 }
 
@@ -102,7 +155,7 @@ int route_prepare(nmg_engine* h, uint32_t grid, const std::vector<uint32_t>& ran
   if (rc) return rc;
   const int rc2 = stage_h2d(h, h->rpool.d_chunk0, c0.data(), (grid + 1) * 4);
   if (rc2) return rc2;
-  h->route_sched_key = h->rt.nparts | ((h->flags & kDbgTinyPool) ? 0x80000000u : 0u);
+  h->route_sched_key = route_key(h);
   return NMG_OK;
 }
 
@@ -139,7 +192,8 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
   rp.nparts = h->rt.nparts;
   rp.xl = xl;
   rp.seq0 = seq0;
-  rp.rec16 = h->rpool.d_rec16;
+  rp.pieces = h->rpool.d_pieces;
+  rp.pk = h->rpool.K;
   rp.cmeta = h->rpool.d_cmeta;
   rp.chunk0 = job.chunk0;
   rp.used = h->rpool.d_used;
@@ -163,6 +217,9 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
   sc.pcnt = h->rpool.d_pcnt;
   sc.pbase = h->rpool.d_pbase;
   sc.clist = h->rpool.d_clist;
+  sc.pieces = h->rpool.d_pieces;
+  sc.pool0 = reinterpret_cast<uint64_t>(h->rpool.pool0);
+  sc.pk = h->rpool.K;
   sc.nparts = h->rt.nparts;
   CountParams cp;
   memset(&cp, 0, sizeof(cp));
@@ -191,7 +248,7 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
   lp.pe_ids = h->rt.d_pe_ids;
   lp.pe_lrel = h->rt.d_pe_lrel;
   lp.pe_cmap = h->rt.d_pe_cmap;
-  lp.rec16 = h->rpool.d_rec16;
+  lp.pool0 = h->rpool.pool0;
   lp.cmeta = h->rpool.d_cmeta;
   lp.clist = h->rpool.d_clist;
   lp.items = h->rpool.d_items;
@@ -219,7 +276,8 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
     f.used = h->rpool.d_used;
     f.cmeta = h->rpool.d_cmeta;
     f.cmatch = h->rpool.d_cmatch;
-    f.rec16 = h->rpool.d_rec16;
+    f.pieces = h->rpool.d_pieces;
+  f.pk = h->rpool.K;
     f.bufcnt = h->d_bufcnt + job.index_base;
     f.nb_bufs = (uint32_t)h->bufcnt_stride;
     f.gbits = xl.gbits;
@@ -245,7 +303,8 @@ int route_settle(nmg_engine* h) {
   f.used = h->rpool.d_used;
   f.cmeta = h->rpool.d_cmeta;
   f.cmatch = h->rpool.d_cmatch;
-  f.rec16 = h->rpool.d_rec16;
+  f.pieces = h->rpool.d_pieces;
+  f.pk = h->rpool.K;
   f.bufcnt = h->d_bufcnt;
   f.nb_bufs = (uint32_t)h->bufcnt_stride;
   f.gbits = h->route_xl.gbits;

@@ -219,6 +219,13 @@ class Engine:
         self._c(lib.nmg_debug_route_count(self.h, C.byref(n)))
         return n.value
 
+    def route_pool(self) -> dict:
+        """The partition-first path's chunk pool as the last schedule left it
+        (internal; tests)."""
+        out = (C.c_uint64 * 5)()
+        self._c(lib.nmg_debug_route_pool(self.h, out))
+        return {"piece_log2": out[0], "pieces": out[1], "ids": out[2], "asked": out[3], "bytes": out[4]}
+
     def last_analyze_ms(self) -> float:
         ms = C.c_float()
         self._c(lib.nmg_last_analyze_ms(self.h, C.byref(ms)))
