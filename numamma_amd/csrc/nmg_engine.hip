@@ -642,6 +642,22 @@ extern "C" int nmg_debug_route_pool(nmg_engine* h, uint64_t out[5]) {
   return NMG_OK;
 }
 
+// Internal (not in include/numamma_gpu.h): the compact-record layout (XLayout,
+// nmg_route.h) of the last analysis or streamed chunk that took the
+// partition-first path (tests): out[0..5] = gbits, obits, tbits, wbits, wesc,
+// tbase; zeros when none did
+extern "C" int nmg_debug_route_layout(nmg_engine* h, uint64_t out[6]) {
+  if (!h || !out) return NMG_ERR_INVALID;
+  const XLayout& xl = h->route_last_xl;
+  out[0] = xl.gbits;
+  out[1] = xl.obits;
+  out[2] = xl.tbits;
+  out[3] = xl.wbits;
+  out[4] = xl.wesc;
+  out[5] = xl.tbase;
+  return NMG_OK;
+}
+
 // Internal (not in include/numamma_gpu.h): per-wave phase cycle counts of the
 // last launch made with flag 0x1000, [grid][16 waves][8] u64:
 // load+check, barrier, process, rest, total, windows.  tools/phase_timing.py.

@@ -485,6 +485,7 @@ struct nmg_engine {
   bool route_pending = false;     // per-buffer match counts of the last route analysis not yet summed
   uint32_t route_grid = 0;
   XLayout route_xl{};
+  XLayout route_last_xl{};        // the layout of the last route launch, streamed chunks included (nmg_debug_route_layout)
 
   // kDbgTiming (internal): per-wave phase cycles of the last launch
   DevBuf<uint64_t> d_dbg;

@@ -177,6 +177,7 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
   base.bufcnt = h->d_bufcnt + job.index_base;  // (count slots of the set's first buffer)
   const uint64_t seq0 = (*job.descs)[0].seq;
   h->route_launches++;
+  h->route_last_xl = xl;
   int slot = 0;
   int rc = launch_events(h, &slot);
   if (rc) return rc;

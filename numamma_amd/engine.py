@@ -226,6 +226,14 @@ class Engine:
         self._c(lib.nmg_debug_route_pool(self.h, out))
         return {"piece_log2": out[0], "pieces": out[1], "ids": out[2], "asked": out[3], "bytes": out[4]}
 
+    def route_layout(self) -> dict:
+        """The compact-record layout (XLayout) of the last analysis or streamed
+        chunk that took the partition-first path; zeros when none did
+        (internal; tests)."""
+        out = (C.c_uint64 * 6)()
+        self._c(lib.nmg_debug_route_layout(self.h, out))
+        return dict(zip(("gbits", "obits", "tbits", "wbits", "wesc", "tbase"), (int(x) for x in out)))
+
     def last_analyze_ms(self) -> float:
         ms = C.c_float()
         self._c(lib.nmg_last_analyze_ms(self.h, C.byref(ms)))
