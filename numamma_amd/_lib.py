@@ -284,6 +284,7 @@ _SIGS = {
     "nmg_debug_route_count": (C.c_int, [H, u64p]),
     "nmg_debug_route_pool": (C.c_int, [H, u64p]),
     "nmg_debug_route_layout": (C.c_int, [H, u64p]),
+    "nmg_debug_route_parts": (C.c_int, [H, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nmg_report": (C.c_int, [H, C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options), C.c_char_p]),
     "nmg_report_host": (C.c_int, [C.POINTER(nmg_host_results), C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options), C.c_char_p]),
     "nmg_run_replay": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32]),

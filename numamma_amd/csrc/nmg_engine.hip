@@ -658,6 +658,21 @@ extern "C" int nmg_debug_route_layout(nmg_engine* h, uint64_t out[6]) {
   return NMG_OK;
 }
 
+// Internal (not in include/numamma_gpu.h): the first key of every partition
+// of the current table's partition-first cut (build_partitions), ascending
+// (tests: the crafted replays of tests/local_lane_cases.py restate the cut);
+// *len = their number, 0 when the table takes no partition-first path
+extern "C" int nmg_debug_route_parts(nmg_engine* h, uint64_t* starts, size_t n, size_t* len) {
+  if (!h || !len) return NMG_ERR_INVALID;
+  const RouteTable& rt = h->rt;
+  *len = rt.ok ? rt.nparts : 0;
+  if (!starts || !*len) return NMG_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(starts, rt.d_pbounds.get(), std::min(n, *len) * 8, hipMemcpyDeviceToHost));
+  return NMG_OK;
+}
+
 // Internal (not in include/numamma_gpu.h): per-wave phase cycle counts of the
 // last launch made with flag 0x1000, [grid][16 waves][8] u64:
 // load+check, barrier, process, rest, total, windows.  tools/phase_timing.py.

@@ -1210,6 +1210,17 @@ __device__ __forceinline__ T l2_load(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The LDS reads of a pair of chunks, whole and in registers from here on: the
+// compiler may neither sink one chunk's read behind the other chunk's
+// arithmetic nor narrow a read into a conditional second one (no instruction
+// of its own: the wait that the first use needed anyway moves here)
+__device__ __forceinline__ void lds_pair(uint4& a, uint4& b) {
+  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));
+}
+__device__ __forceinline__ void lds_pair(uint2& a, uint2& b) {
+  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y));
+}
+
 // A partition owns a range of table positions; the counters are indexed by
 // entry id, which is the position for the nmg_set_objects table and
 // pe_ids[position] for an online table (nmg_update_objects).
@@ -1239,7 +1250,11 @@ __device__ __forceinline__ int32_t match_older_pos(const Params& p, uint32_t fir
 // EXTRA: the outputs of NMG_F_OBJECT_LEVELS, NMG_F_SAMPLE_MATCHES, the access timeline and the page cost cells (the
 // extras block at the end of `process`; again a variant of its own: the
 // instances without it are the code they were before it existed)
-template <bool TIMING, bool PACKED, bool EXTRA>
+// INSTR: the instrumented instance, for kDbgLocalTiming's stamps and the
+// ablation switches (kDbgLocalNoWork / NoSearch / NoObj / NoPage / Atomics):
+// launch_local picks it when one of them is set, and only it reads them -- a
+// default engine's chunk loop carries none of those scalars
+template <bool INSTR, bool PACKED, bool EXTRA>
 __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   __shared__ uint64_t s_keys[kPartSlots];
   __shared__ uint4 s_pn[kPartSlots];  // packed node records (PackedNode)
@@ -1263,9 +1278,15 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   RTimer rt;  // (kDbgLocalTiming) per-wave phase cycles
 #pragma unroll
   for (int k = 0; k < 12; k++) rt.acc[k] = 0;
-  rt.last = TIMING ? stamp() : 0;
+  const bool tim = INSTR && (p.flags & kDbgLocalTiming) != 0;
+  const bool nowork = INSTR && (p.flags & kDbgLocalNoWork) != 0, nosearch = INSTR && (p.flags & kDbgLocalNoSearch) != 0;
+  const bool noobj = INSTR && (p.flags & kDbgLocalNoObj) != 0, nopage = INSTR && (p.flags & kDbgLocalNoPage) != 0;
+  auto lstamp = [&](int i) {
+    if (INSTR && tim) rt_stamp<true>(rt, i);
+  };
+  rt.last = tim ? stamp() : 0;
   uint32_t nchunks = 0, nit = 0;
-  uint64_t textra = 0;  // (TIMING) cycles of the extras block
+  uint64_t textra = 0;  // (kDbgLocalTiming) cycles of the extras block
   uint32_t nfound = 0;  // this wave's matched records (Params::found, added once per workgroup at the end)
   if (tid == 0) s_nfound = 0;  // (read after the item loop's barriers)
   // the item counters start zeroed; every flush re-zeroes what it reads
@@ -1296,7 +1317,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
   while (true) {
     lds_sync();
     const uint32_t it = __builtin_amdgcn_readfirstlane(s_item);
-    rt_stamp<TIMING>(rt, 6);
+    lstamp(6);
     if (it >= nitems) break;
     nit++;
     const uint4 item = s_nx[0];
@@ -1358,53 +1379,61 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       s_took = 0;
     }
     const uint32_t ncell = (pages && pi.pages_lds) ? T * pi.span : 0u;
-    const bool excl = item.w != 0 && !(p.flags & kDbgLocalAtomics);  // no other workgroup writes this partition's
-                                                                     // counters
+    // no other workgroup writes this partition's counters
+    const bool excl = item.w != 0 && !(INSTR && (p.flags & kDbgLocalAtomics));
     if (tid == 0) s_big = 0;
     lds_sync();
     const uint64_t k0key = u64of(__builtin_amdgcn_readfirstlane((uint32_t)s_keys[0]),
                                  __builtin_amdgcn_readfirstlane((uint32_t)(s_keys[0] >> 32)));
-    rt_stamp<TIMING>(rt, 7);
+    lstamp(7);
 
     // Each wave takes pairs of consecutive chunks of the item's list (in
     // LDS) from an LDS counter, so the waves end within a pair of each other
-    // at the item's barrier, and works on two chunks at a time, their steps interleaved
-    // (the LDS round trips of one cover the other's); the records of the next
-    // two are in flight meanwhile (a wave's chunk is 1.5 KiB).  The compiler
-    // waits for a chunk's loads with the smallest vmcnt any path allows, so
-    // the loop is shaped for that: unrolled (the record registers are never
-    // copied -- a copy of a load in flight waits for it), every chunk load
-    // covers the whole wave (a fixed number of memory ops between a load and
-    // its use), and the rare paths that issue global memory ops of their own
-    // end with vmcnt(0).
+    // at the item's barrier, and works on the two chunks of a pair together:
+    // the common path is straight-line code over both -- for every step the
+    // LDS reads of both chunks are issued with in-range indices (a lane
+    // without a record reads element 0), then both are decided with selects,
+    // so one round trip serves the pair; only the LDS atomics are predicated
+    // per lane, and everything rare sits behind a ballot.  The records of the
+    // next two chunks are in flight meanwhile (a wave's chunk is 1.5 KiB).  The
+    // compiler waits for a chunk's loads with the smallest vmcnt any path
+    // allows, so the loop is shaped for that: unrolled (the source never
+    // copies the record registers -- a copy of a load in flight waits for it),
+    // every chunk load covers the whole wave (a fixed number of memory ops
+    // between a load and its use), and the rare paths that issue global memory
+    // ops of their own end with vmcnt(0).  (What the compiler makes of it:
+    // DESIGN 7.0r14 -- group B is waited for with vmcnt(3), then 2; group A's
+    // first decode steps are hoisted into the latch ahead of B's second load,
+    // so A is waited for with vmcnt(2), then 1, three loads in flight.)
     const uint32_t nl = item.z - item.y;
     auto chunk_load = [&](uint32_t l, uint4& a) {  // the chunk at list position l (l >= nl: none; no branch)
       // (the chunk's place in the pool's pieces was resolved by scatter_kernel; none: the pool's lowest chunk)
       const uint32_t e = l < nl ? s_coff[l] : 0u;
       a = lp.pool0[uint64_t(e) * kChunk + lane];
     };
-    // the kLC chunks at list positions l0, l0 + 1, ... (past the list: no valid lane)
+    // the kLC chunks at list positions l0 < nl, l0 + 1, ... (past the list: no valid lane)
     auto process = [&](uint32_t l0, const uint4 (&a16)[kLC]) {
-      uint32_t li[kLC];
+      uint32_t li[kLC], cw[kLC];  // list position and list word (fill | chunk id)
       bool valid[kLC];
       uint64_t addr[kLC], ts[kLC], w[kLC];
       XRec xr[kLC];
 #pragma unroll
       for (int j = 0; j < kLC; j++) {
         li[j] = l0 + j;
-        const uint32_t fill = li[j] < nl ? s_clist[li[j]] >> kChunkIdBits : 0u;
-        valid[j] = (uint32_t)lane < fill;
+        cw[j] = s_clist[min(li[j], nl - 1)];
       }
-      if (TIMING) {  // (timing: these chunks' loads count as wait; the other group's kLC loads are younger)
+#pragma unroll
+      for (int j = 0; j < kLC; j++) valid[j] = (uint32_t)lane < (li[j] < nl ? cw[j] >> kChunkIdBits : 0u);
+      if (INSTR && tim) {  // (timing: these chunks' loads count as wait; the other group's kLC loads are younger)
         asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // (kLC)
         nchunks += kLC;
       }
-      rt_stamp<TIMING>(rt, 0);
-      if (p.flags & kDbgLocalNoWork) {  // (ablation) loads only
+      lstamp(0);
+      if (INSTR && nowork) {  // (ablation) loads only
 #pragma unroll
         for (int j = 0; j < kLC; j++)
           if (lane == 0 && li[j] < nl)
-            lp.cmatch[s_clist[li[j]] & ((1u << kChunkIdBits) - 1)] = a16[j].x ^ a16[j].y ^ a16[j].z ^ a16[j].w;
+            lp.cmatch[cw[j] & ((1u << kChunkIdBits) - 1)] = a16[j].x ^ a16[j].y ^ a16[j].z ^ a16[j].w;
         return;
       }
       // (update_counters of every routed SAMPLE: the route pass).  The common
@@ -1433,102 +1462,113 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         ts[j] = xr[j].ts;      // offset from tbase (escaped: absolute)
         w[j] = valid[j] ? xr[j].w : 0ull;
       }
-      rt_stamp<TIMING>(rt, 1);
+      lstamp(1);
       // lower bound among the partition's keys (ht_lower_key, tools/hash.c:63-77):
       // the record's address is >= the partition's first key and < the next
       // partition's.  The directory slot gives the largest key <= the slot
       // start, the keys inside the slot and the first kDirInline of their
       // offsets: the answer is that key plus the offsets <= the record's; keys
       // are read only past them (or for a slot whose offsets do not fit).
-      int32_t r[kLC];
-      uint32_t sa[kLC], sn[kLC];
+      uint32_t slot[kLC], sa[kLC], sn[kLC];
+      uint4 de[kLC];
+#pragma unroll
+      for (int j = 0; j < kLC; j++)
+        slot[j] = valid[j] ? (uint32_t)min(addr[j] >> dshift, (uint64_t)(kPartDir - 1)) : 0u;
+#pragma unroll
+      for (int j = 0; j < kLC; j++) de[j] = s_dir[slot[j]];
+      static_assert(kLC == 2, "lds_pair: two chunks");
+      lds_pair(de[0], de[1]);
 #pragma unroll
       for (int j = 0; j < kLC; j++) {
-        r[j] = -1;
-        sa[j] = sn[j] = 0;
-        if (valid[j]) {
-          const uint32_t slot = (uint32_t)min(addr[j] >> dshift, (uint64_t)(kPartDir - 1));
-          const uint4 de = s_dir[slot];
-          const uint32_t lo = de.x & 1023u, n = (de.x >> 10) & 2047u;
-          uint32_t a = lo, m = n;
-          if (n && ((de.x >> 21) & 1u)) {  // inline offsets
-            const uint64_t rs64 = addr[j] - (uint64_t(slot) << dshift);
-            const uint32_t rs = rs64 >> 16 ? 0x10000u : (uint32_t)rs64;
-            const uint32_t c = (uint32_t)((de.y & 0xffffu) <= rs) + (uint32_t)((de.y >> 16) <= rs) +
-                               (uint32_t)((de.z & 0xffffu) <= rs) + (uint32_t)((de.z >> 16) <= rs) +
-                               (uint32_t)((de.w & 0xffffu) <= rs) + (uint32_t)((de.w >> 16) <= rs);
-            a = lo + min(c, n);
-            m = (c == kDirInline && n > kDirInline) ? n - kDirInline : 0u;  // past the listed keys: search
-          }
-          sa[j] = a;  // answer in [a, a + m]: keys[a] <= addr
-          sn[j] = m;
-          r[j] = 0;
-        }
+        const uint32_t lo = de[j].x & 1023u, n = (de[j].x >> 10) & 2047u;
+        const bool inl = n && ((de[j].x >> 21) & 1u);  // inline offsets
+        const uint64_t rs64 = addr[j] - (uint64_t(slot[j]) << dshift);
+        const uint32_t rs = rs64 >> 16 ? 0x10000u : (uint32_t)rs64;
+        const uint32_t c = (uint32_t)((de[j].y & 0xffffu) <= rs) + (uint32_t)((de[j].y >> 16) <= rs) +
+                           (uint32_t)((de[j].z & 0xffffu) <= rs) + (uint32_t)((de[j].z >> 16) <= rs) +
+                           (uint32_t)((de[j].w & 0xffffu) <= rs) + (uint32_t)((de[j].w >> 16) <= rs);
+        const uint32_t a = inl ? lo + min(c, n) : lo;
+        // (inline and past the listed keys: search the rest)
+        const uint32_t m = !inl ? n : (c == kDirInline && n > kDirInline) ? n - kDirInline : 0u;
+        sa[j] = valid[j] ? a : 0u;  // answer in [a, a + m]: keys[a] <= addr
+        sn[j] = valid[j] ? m : 0u;
       }
-      if (TIMING) {  // (records whose lookup reads keys)
+      if (INSTR && tim) {  // (records whose lookup reads keys)
 #pragma unroll
         for (int j = 0; j < kLC; j++) rt.acc[11] += (uint64_t)__popcll(__ballot(sn[j] != 0));
       }
+      // one loop for the pair, to the deeper of the two searches: a chunk
+      // that is done sits still (half = 0: it re-reads keys[a], and moves nothing)
+      {
+        bool more = false;
 #pragma unroll
-      for (int j = 0; j < kLC; j++) {
-        uint32_t a = sa[j], n = sn[j];
-        while (n) {
-          const uint32_t half = (n + 1) >> 1;
-          if (s_keys[a + half] - k0key <= addr[j]) {
-            a += half;
-            n -= half;
-          } else {
-            n = half - 1;
+        for (int j = 0; j < kLC; j++) more |= sn[j] != 0;
+        while (more) {
+          uint32_t half[kLC];
+          uint64_t key[kLC];
+#pragma unroll
+          for (int j = 0; j < kLC; j++) {
+            half[j] = (sn[j] + 1) >> 1;
+            key[j] = s_keys[sa[j] + half[j]];
+          }
+          more = false;
+#pragma unroll
+          for (int j = 0; j < kLC; j++) {
+            const bool le = key[j] - k0key <= addr[j];
+            sa[j] += le ? half[j] : 0u;
+            sn[j] = le ? sn[j] - half[j] : half[j] - (uint32_t)(sn[j] != 0);  // (done: 0 - 0 either way)
+            more |= sn[j] != 0;
           }
         }
-        if (r[j] >= 0) r[j] = (int32_t)a;
       }
-      if (TIMING) {  // (the search ends here)
+      if (INSTR && tim) {  // (the search ends here)
         bool any = false;
 #pragma unroll
-        for (int j = 0; j < kLC; j++) any |= r[j] >= 0;
+        for (int j = 0; j < kLC; j++) any |= valid[j];
         (void)__builtin_amdgcn_readfirstlane(__ballot(any));
       }
-      rt_stamp<TIMING>(rt, 2);
+      lstamp(2);
       // is_sample_in_buffer (mem_analyzer.c:141-155) on the key's newest
       // entry, from its packed node record: the object starts at the key, so
       // key <= addr < end is addr - first key < end - first key; the dates
       // compare quantised, a timestamp in the quantum of either bound (or an
       // exact-marked key, or an escaped record) is decided on the exact node
+      const uint32_t (&r)[kLC] = sa;  // the key's slot (a lane without a record: 0)
       int32_t erel[kLC];
       uint64_t pofs[kLC];  // a match: addr - buffer_addr
       uint32_t hrel[kLC], pnw[kLC], tq[kLC];
       bool older[kLC], amb[kLC];
+      {
+        uint4 pn[kLC];
+        uint2 inf[kLC];
 #pragma unroll
-      for (int j = 0; j < kLC; j++) {
-        erel[j] = -1;
-        pofs[j] = 0;
-        hrel[j] = kEmpty32;
-        older[j] = false;
-        amb[j] = false;
-        pnw[j] = 0;
-        // (the offsets are < 2^40: the timestamp's quantum fits 32 bits)
-        tq[j] = __builtin_amdgcn_alignbit((uint32_t)(ts[j] >> 32), (uint32_t)ts[j], kPnQShift);
-        if (r[j] >= 0 && !(p.flags & kDbgLocalNoSearch)) {
-          const uint4 pn = s_pn[r[j]];
-          const uint2 inf = s_info[r[j]];
-          pnw[j] = pn.w;
-          const bool in = addr[j] >= (uint64_t)inf.y && addr[j] < (uint64_t)pn.x;
-          amb[j] = xr[j].esc || (pn.w & kPnExact) || (in && (tq[j] == pn.y || tq[j] == pn.z));
-          if (!amb[j] && in && tq[j] > pn.y && tq[j] < pn.z) {
-            erel[j] = (int32_t)(pn.w & 2047u);
-            pofs[j] = addr[j] - inf.y;
-            hrel[j] = inf.x;
-          } else if (!amb[j]) {
-            older[j] = (pn.w & kPnOlder) != 0;
-          }
+        for (int j = 0; j < kLC; j++) {
+          pn[j] = s_pn[r[j]];
+          inf[j] = s_info[r[j]];
+        }
+        lds_pair(pn[0], pn[1]);
+        lds_pair(inf[0], inf[1]);
+#pragma unroll
+        for (int j = 0; j < kLC; j++) {
+          // (the offsets are < 2^40: the timestamp's quantum fits 32 bits)
+          tq[j] = __builtin_amdgcn_alignbit((uint32_t)(ts[j] >> 32), (uint32_t)ts[j], kPnQShift);
+          // (bitwise: nothing here is worth a branch)
+          const bool live = valid[j] & !(INSTR && nosearch);
+          const bool in = (addr[j] >= (uint64_t)inf[j].y) & (addr[j] < (uint64_t)pn[j].x);
+          amb[j] = live & (xr[j].esc | ((pn[j].w & kPnExact) != 0) | (in & ((tq[j] == pn[j].y) | (tq[j] == pn[j].z))));
+          const bool hit = live & !amb[j] & in & (tq[j] > pn[j].y) & (tq[j] < pn[j].z);
+          erel[j] = hit ? (int32_t)(pn[j].w & 2047u) : -1;
+          pofs[j] = hit ? addr[j] - inf[j].y : 0ull;
+          hrel[j] = hit ? inf[j].x : kEmpty32;
+          older[j] = live & !amb[j] & !hit & ((pn[j].w & kPnOlder) != 0);
+          pnw[j] = live ? pn[j].w : 0u;
         }
       }
       bool anyamb = false;
 #pragma unroll
       for (int j = 0; j < kLC; j++) {
         anyamb |= amb[j];
-        if (TIMING) rt.acc[10] += (uint64_t)__popcll(__ballot(amb[j]));  // (records decided on the exact node)
+        if (INSTR && tim) rt.acc[10] +=(uint64_t)__popcll(__ballot(amb[j]));  // (records decided on the exact node)
       }
       if (__ballot(anyamb)) {  // (rare) the exact node record, from global memory
 #pragma unroll
@@ -1599,18 +1639,18 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       // the group), and this wave's matched total
       {
         uint64_t mine = 0;
-        uint32_t ml = 0;
+        uint32_t ml = 0, mc = 0;
 #pragma unroll
         for (int j = 0; j < kLC; j++) {
           const uint64_t fm = __ballot(erel[j] >= 0);
           nfound += (uint32_t)__popcll(fm);
           mine = lane == j ? fm : mine;
           ml = lane == j ? li[j] : ml;
+          mc = lane == j ? cw[j] : mc;
         }
-        if (lane < kLC && ml < nl) lp.cmatch[s_clist[ml] & ((1u << kChunkIdBits) - 1)] = mine;
+        if (lane < kLC && ml < nl) lp.cmatch[mc & ((1u << kChunkIdBits) - 1)] = mine;
       }
-      rt_stamp<TIMING>(rt, 3);
-      const bool noobj = (p.flags & kDbgLocalNoObj) != 0;
+      lstamp(3);
 #pragma unroll
       for (int j = 0; j < kLC; j++) {
         bool ok = erel[j] >= 0 && !noobj && w[j] < kLaneMaxWeight;
@@ -1637,13 +1677,13 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       if (!noobj) {  // (read first: an unconditional LDS min per match was 9 % slower, hot entries)
         unsigned long long cur[kLC];
 #pragma unroll
-        for (int j = 0; j < kLC; j++) cur[j] = erel[j] >= 0 ? s_first[erel[j]] : 0ull;
+        for (int j = 0; j < kLC; j++) cur[j] = s_first[erel[j] >= 0 ? erel[j] : 0];  // (no match: entry 0, unused)
 #pragma unroll
         for (int j = 0; j < kLC; j++)
           if (erel[j] >= 0 && xr[j].loc < cur[j]) atomicMin(&s_first[erel[j]], (unsigned long long)xr[j].loc);
       }
-      rt_stamp<TIMING>(rt, 4);
-      if (pages && !(p.flags & kDbgLocalNoPage)) {
+      lstamp(4);
+      if (pages && !nopage) {
         // ma_get_block: page_no = (int)((addr - buffer_addr) / 4096) (mem_analyzer.c:530-531)
         uint32_t page[kLC];
         bool glob = false;
@@ -1671,7 +1711,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
           vm_drain();
         }
       }
-      rt_stamp<TIMING>(rt, 5);
+      lstamp(5);
       if (EXTRA) {
         // The extras: every record's match at its arena position
         // (Params::smatch, as attribute_kernel leaves it), and the matched
@@ -1776,7 +1816,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
           }
           vm_drain();
         }
-        if (TIMING) {
+        if (INSTR && tim) {
           const uint64_t now = stamp();
           textra += now - rt.last;
           rt.last = now;
@@ -1809,7 +1849,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     if (lane == 0) won = atomicExch(&s_took, 1u) == 0 ? 1u : 0u;
     if (__builtin_amdgcn_readfirstlane(won)) take_next();
     lds_sync();
-    rt_stamp<TIMING>(rt, 9);  // (waiting for the item's slowest wave)
+    lstamp(9);  // (waiting for the item's slowest wave)
     // an item alone on its partition whose counters nothing else wrote since
     // the reset (no overflow-path record in this launch, no large weight in
     // this item) stores them without reading: counts and weights from zero,
@@ -1861,7 +1901,8 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
     {
       const uint32_t nw = (ncell + 1) / 2, span = pi.span;
       const uint32_t cmap = PACKED ? __builtin_amdgcn_readfirstlane(pi.cmap) : ~0u;
-      const uint32_t smag = span ? 0xffffffffu / span + 1u : 0u;
+      // (span 1 -- a partition of one key whose object lies in one page -- has no 32-bit magic: the row is the cell)
+      const uint32_t smag = span > 1 ? 0xffffffffu / span + 1u : 0u;
       constexpr uint32_t kU = 4;
       for (uint32_t j0 = tid; j0 < nw; j0 += kU * kLWG) {
         uint32_t cnt[kU][2], old[kU][2];
@@ -1874,7 +1915,7 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
 #pragma unroll
           for (uint32_t h = 0; h < 2; h++) {
             cnt[u][h] = (v >> (16 * h)) & 0xffffu;
-            const uint32_t li = 2 * j + h, th = __umulhi(li, smag), rel = li - th * span;
+            const uint32_t li = 2 * j + h, th = span == 1 ? li : __umulhi(li, smag), rel = li - th * span;
             uint64_t cell = pi.cb + rel;
             if (cmap != ~0u) cell = cnt[u][h] ? lp.pe_cmap[cmap + rel] : 0u;  // (online: packed cells)
             pc[u][h] = p.hist + uint64_t(th) * p.hist_cells + cell;
@@ -1892,12 +1933,12 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
       }
     }
     lds_sync();
-    rt_stamp<TIMING>(rt, 8);
+    lstamp(8);
   }
   if (lane == 0 && nfound) atomicAdd(&s_nfound, nfound);  // (one add to Params::found per workgroup)
   lds_sync();
   if (tid == 0 && s_nfound) atomicAdd(p.found, (unsigned long long)s_nfound);
-  if (TIMING && lane == 0) {
+  if (INSTR && tim && lane == 0) {
     unsigned long long* o = p.dbg + (uint64_t(blockIdx.x) * (kWG / 64) + tid / 64) * kRouteTimingWords;
     for (int k = 0; k < 9; k++) o[k] = rt.acc[k];
     o[9] = nchunks;
@@ -1985,22 +2026,25 @@ hipError_t launch_scatter(uint32_t grid, hipStream_t s, const ScatterParams& r) 
   return hipGetLastError();
 }
 
-template <bool TIMING, bool PACKED>
+template <bool INSTR, bool PACKED>
 static void launch_local_as(bool extra, uint32_t grid, hipStream_t s, const LocalParams& r) {
-  if (extra) hipLaunchKernelGGL((local_kernel<TIMING, PACKED, true>), dim3(grid), dim3(kLWG), 0, s, r);
-  else hipLaunchKernelGGL((local_kernel<TIMING, PACKED, false>), dim3(grid), dim3(kLWG), 0, s, r);
+  if (extra) hipLaunchKernelGGL((local_kernel<INSTR, PACKED, true>), dim3(grid), dim3(kLWG), 0, s, r);
+  else hipLaunchKernelGGL((local_kernel<INSTR, PACKED, false>), dim3(grid), dim3(kLWG), 0, s, r);
 }
 
-// the extras variant for engines with per-object levels or per-sample matches
+// the extras variant for engines with per-object levels or per-sample matches;
+// the instrumented one for the timing stamps and the ablation switches
 hipError_t launch_local(uint32_t grid, hipStream_t s, const LocalParams& r) {
-  const bool timing = (r.p.flags & kDbgLocalTiming) != 0, packed = r.pe_cmap != nullptr;
+  constexpr uint32_t kInstr = kDbgLocalTiming | kDbgLocalNoWork | kDbgLocalNoSearch | kDbgLocalNoObj |
+                              kDbgLocalNoPage | kDbgLocalAtomics;
+  const bool instr = (r.p.flags & kInstr) != 0, packed = r.pe_cmap != nullptr;
   const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr || r.p.tl != nullptr ||
                      r.p.cost != nullptr;
   if (packed) {
-    if (timing) launch_local_as<true, true>(extra, grid, s, r);
+    if (instr) launch_local_as<true, true>(extra, grid, s, r);
     else launch_local_as<false, true>(extra, grid, s, r);
   } else {
-    if (timing) launch_local_as<true, false>(extra, grid, s, r);
+    if (instr) launch_local_as<true, false>(extra, grid, s, r);
     else launch_local_as<false, false>(extra, grid, s, r);
   }
   return hipGetLastError();

@@ -234,6 +234,17 @@ class Engine:
         self._c(lib.nmg_debug_route_layout(self.h, out))
         return dict(zip(("gbits", "obits", "tbits", "wbits", "wesc", "tbase"), (int(x) for x in out)))
 
+    def route_parts(self) -> np.ndarray:
+        """The first key of every partition of the current table's
+        partition-first cut, ascending; empty when the table has none
+        (internal; tests)."""
+        n = C.c_size_t(0)
+        self._c(lib.nmg_debug_route_parts(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            self._c(lib.nmg_debug_route_parts(self.h, _ptr(out, C.c_uint64), n.value, C.byref(n)))
+        return out
+
     def last_analyze_ms(self) -> float:
         ms = C.c_float()
         self._c(lib.nmg_last_analyze_ms(self.h, C.byref(ms)))

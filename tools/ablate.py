@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Kernel ablation on the GPU: time nmg::attribute_kernel with parts of its
 work switched off, interleaved in one process (cdna_hip_programming.md
-§5.4 rule 24).  Prints one JSON line per (workload, variant)."""
+§5.4 rule 24).  Prints one JSON line per (workload, variant).
+
+The local pass's switches (route_atomics, route_noloc, local_*) select
+local_kernel's instrumented instance, which alone reads them; "route" (flags
+0x3) runs the plain instance a default engine launches, whose chunk loop is
+about an eighth shorter and spills half the scalars.  Compare the
+local_* variants with each other; against "route" a difference holds the
+instance's own cost too."""
 import argparse
 import json
 import os
