@@ -415,32 +415,21 @@ extern "C" uint32_t nmg_get_nb_buffers(nmg_engine* h) {
   return h->counts_override ? (uint32_t)h->ov_samples.size() : (uint32_t)h->descs.size();
 }
 
-// What the call-site registry reads per entry (buffer_size, first_ordinal,
-// count_weight), set in res in the report's walk order: the id order, or, for
-// live online tables, the order of the latest table that listed every entry
-// (h->order; meta follows it), with w.pos the walk position of each id.
-int walk_counters(nmg_engine* h, const HostResults& r, nmg_host_results& res, WalkCounters& w) {
-  const uint32_t E = h->E;
-  res.nb_entries = E;
+// (ReportInput, nmg_engine_impl.h; the permutation itself is nmg_walk_order.h's)
+int report_begin(nmg_engine* h, ReportInput& in) {
+  int rc = engine_download(h, in.r, true, false);  // (the total only: no found_kernel)
+  if (rc) return rc;
+  nmg_host_results& res = in.res;
+  memset(&res, 0, sizeof(res));
+  res.nb_threads = h->T;
+  res.match_samples = 1;
+  res.nb_entries = h->E;
   res.buffer_size = h->tab.buffer_size.data();
-  res.first_ordinal = r.first.data();
-  res.count_weight = r.count_weight.data();
+  res.first_ordinal = in.r.first.data();
+  res.count_weight = in.r.count_weight.data();
   if (h->order.empty()) return NMG_OK;
-  if (h->order.size() != E) return fail(h, NMG_ERR_STATE, "report walk order does not cover every entry");
-  w.pos.resize(E);
-  w.size.resize(E);
-  w.first.resize(E);
-  w.cw.resize((size_t)E * 4);
-  for (uint32_t k = 0; k < E; k++) {
-    const uint32_t id = h->order[k];
-    w.pos[id] = k;
-    w.size[k] = h->tab.buffer_size[id];
-    w.first[k] = r.first[id];
-    for (int q = 0; q < 4; q++) w.cw[(size_t)k * 4 + q] = r.count_weight[(size_t)id * 4 + q];
-  }
-  res.buffer_size = w.size.data();
-  res.first_ordinal = w.first.data();
-  res.count_weight = w.cw.data();
+  if (h->order.size() != h->E) return fail(h, NMG_ERR_STATE, "report walk order does not cover every entry");
+  walk_permute(h->order.data(), h->E, &res.buffer_size, &res.first_ordinal, &res.count_weight, in.w);
   return NMG_OK;
 }
 
@@ -449,24 +438,27 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   Range range("nmg_report");
   if (!h || (h->E && !meta)) return NMG_ERR_INVALID;
   if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_report before nmg_set_objects");
+  if (!h->order.empty() && opts && opts->dump_flags)
+    return fail(h, NMG_ERR_STATE, "dump modes need the entries in id order");
   const bool timing = getenv("NMG_REPORT_TIMING") != nullptr;  // phase times on stderr
   auto t0 = std::chrono::steady_clock::now();
-  HostResults r;
-  int rc = engine_download(h, r, true, false);  // (the total only: no found_kernel)
+  ReportInput in;
+  int rc = report_begin(h, in);
   if (rc) return rc;
+  const HostResults& r = in.r;
+  nmg_host_results& res = in.res;
   auto t1 = std::chrono::steady_clock::now();
   std::vector<uint32_t> rows;
   int64_t ncells = 0;
   if ((h->flags & NMG_F_PAGE_HIST) && (!opts || opts->dump_single_items)) {
-    rc = collect_page_cells(h, &rows, &ncells);
+    rc = rows_collect(h, h->cprep.rows, cells_prepare, &rows, cells_fill);
     if (rc) return rc;
+    ncells = h->cprep.rows.n;
   }
   if (timing)
     fprintf(stderr, "nmg_report: counters D2H %.3f s, page cells D2H + rows %.3f s (%" PRId64 " cells)\n",
             std::chrono::duration<double>(t1 - t0).count(),
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count(), ncells);
-  nmg_host_results res;
-  memset(&res, 0, sizeof(res));
   res.global[0] = r.global[0];
   res.global[1] = r.global[1];
   res.nb_buffers = (uint32_t)r.buf_samples.size();
@@ -475,35 +467,16 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   res.buf_bytes = r.buf_bytes.data();
   res.cells = rows.data();
   res.nb_cells = ncells;
-  res.nb_threads = h->T;
   res.match_samples = (h->flags & NMG_F_MATCH_SAMPLES) ? 1 : 0;
   res.objects = h->tab.objects.data();
-  // live online tables: entries walked in the order of the latest table that
-  // listed them all (ids are creation order there); meta follows that order
-  WalkCounters w;
+  // live online tables: meta follows the walk order (ids are creation order
+  // there), and so do the objects and the page rows, grouped by walk position
   std::vector<nmg_object> w_obj;
   std::vector<uint32_t> w_rows;
-  if (!h->order.empty() && opts && opts->dump_flags)
-    return fail(h, NMG_ERR_STATE, "dump modes need the entries in id order");
-  rc = walk_counters(h, r, res, w);
-  if (rc) return rc;
   if (!h->order.empty()) {
-    const uint32_t E = h->E;
-    const std::vector<uint32_t>& pos = w.pos;
-    w_obj.resize(E);
-    for (uint32_t k = 0; k < E; k++) w_obj[k] = h->tab.objects[h->order[k]];
-    // page rows (entry, thread, page, count), grouped by walk position
-    std::vector<uint32_t> idx((size_t)ncells);
-    for (uint32_t i = 0; i < (uint32_t)ncells; i++) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return pos[rows[4 * a]] < pos[rows[4 * b]]; });
-    w_rows.resize(rows.size());
-    for (size_t i = 0; i < idx.size(); i++) {
-      const uint32_t* q = &rows[4 * (size_t)idx[i]];
-      w_rows[4 * i] = pos[q[0]];
-      w_rows[4 * i + 1] = q[1];
-      w_rows[4 * i + 2] = q[2];
-      w_rows[4 * i + 3] = q[3];
-    }
+    w_obj.resize(h->E);
+    for (uint32_t k = 0; k < h->E; k++) w_obj[k] = h->tab.objects[h->order[k]];
+    w_rows = walk_regroup_rows(rows.data(), ncells, in.w.pos);
     res.cells = w_rows.data();
     res.objects = w_obj.data();
   }
@@ -541,60 +514,41 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
   return rc;
 }
 
-// The timeline rows and the counters the call-site registry needs, handed to
-// the host writer (entries in the report's walk order, as nmg_report).
+// A row set and what the call-site registry needs (report_begin), handed to
+// a host writer that groups the rows by site: they go in any order.
+template <class RS, class Prepare, class Write>
+static int report_rows(nmg_engine* h, RS& s, Prepare prepare, Write write) {
+  ReportInput in;
+  int rc = report_begin(h, in);
+  if (rc) return rc;
+  std::vector<typename RS::word> rows;
+  rc = rows_collect(h, s, prepare, &rows);
+  if (rc) return rc;
+  walk_rewrite_entries(rows.data(), s.n, RS::kWords, in.w.pos);
+  std::string err;
+  rc = write(&in.res, rows.data(), s.n, err);
+  if (rc && !err.empty()) h->last_error = err;
+  return rc;
+}
+
 extern "C" int nmg_report_timeline(nmg_engine* h, const nmg_object_meta* meta, const nmg_report_options* opts) {
   Range range("nmg_report_timeline");
   if (!h || (h->E && !meta)) return NMG_ERR_INVALID;
   if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_report_timeline before nmg_set_objects");
   if (!h->tl.on) return fail(h, NMG_ERR_STATE, "no timeline set (nmg_set_timeline)");
-  HostResults r;
-  int rc = engine_download(h, r, true, false);
-  if (rc) return rc;
-  std::vector<uint32_t> rows;
-  int64_t n = 0;
-  rc = collect_timeline_cells(h, &rows, &n);
-  if (rc) return rc;
-  nmg_host_results res;
-  memset(&res, 0, sizeof(res));
-  res.nb_threads = h->T;
-  res.match_samples = 1;
-  WalkCounters w;
-  rc = walk_counters(h, r, res, w);
-  if (rc) return rc;
-  for (int64_t i = 0; i < n && !w.pos.empty(); i++) rows[5 * i] = w.pos[rows[5 * i]];  // (the writer groups by site: any order)
-  std::string err;
-  rc = write_timeline(&res, meta, opts, &h->tl.opt, rows.data(), n, err);
-  if (rc && !err.empty()) h->last_error = err;
-  return rc;
+  return report_rows(h, h->tl.rows, timeline_prepare, [&](const nmg_host_results* res, const uint32_t* rows, int64_t n, std::string& err) {
+    return write_timeline(res, meta, opts, &h->tl.opt, rows, n, err);
+  });
 }
 
-// The cost rows and the counters the call-site registry needs, handed to the
-// host writer (entries in the report's walk order, as nmg_report).
 extern "C" int nmg_report_page_cost(nmg_engine* h, const nmg_object_meta* meta, const nmg_report_options* opts) {
   Range range("nmg_report_page_cost");
   if (!h || (h->E && !meta)) return NMG_ERR_INVALID;
   if (!h->have_table) return fail(h, NMG_ERR_STATE, "nmg_report_page_cost before nmg_set_objects");
   if (!h->cost.on) return fail(h, NMG_ERR_STATE, "no page cost cells set (nmg_set_page_cost)");
-  HostResults r;
-  int rc = engine_download(h, r, true, false);
-  if (rc) return rc;
-  std::vector<uint64_t> rows;
-  int64_t n = 0;
-  rc = collect_cost_cells(h, &rows, &n);
-  if (rc) return rc;
-  nmg_host_results res;
-  memset(&res, 0, sizeof(res));
-  res.nb_threads = h->T;
-  res.match_samples = 1;
-  WalkCounters w;
-  rc = walk_counters(h, r, res, w);
-  if (rc) return rc;
-  for (int64_t i = 0; i < n && !w.pos.empty(); i++) rows[4 * i] = w.pos[rows[4 * i]];  // (the writer groups by site: any order)
-  std::string err;
-  rc = write_page_cost(&res, meta, opts, rows.data(), n, err);
-  if (rc && !err.empty()) h->last_error = err;
-  return rc;
+  return report_rows(h, h->cost.rows, cost_prepare, [&](const nmg_host_results* res, const uint64_t* rows, int64_t n, std::string& err) {
+    return write_page_cost(res, meta, opts, rows, n, err);
+  });
 }
 
 // Internal (not in include/numamma_gpu.h; bench.py): the first kernel's

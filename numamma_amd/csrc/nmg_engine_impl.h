@@ -38,6 +38,7 @@
 #include "nmg_kernels.h"
 #include "nmg_pool_layout.h"
 #include "nmg_route.h"
+#include "nmg_walk_order.h"
 
 using namespace nmg;
 
@@ -254,6 +255,19 @@ struct CellLayout {
   int ensure(nmg_engine* h, uint64_t E, uint64_t nsent);  // (re)allocated when the table outgrows them
 };
 
+// The rows of one product (DESIGN.md "Row sets"): n rows of WORDS words on the
+// device and the results epoch they were prepared in (0: none).  Served by
+// rows_count / rows_get / rows_collect below.
+template <class W, uint32_t WORDS>
+struct RowSet {
+  using word = W;
+  static constexpr uint32_t kWords = WORDS;
+  DevBuf<W> d_rows;
+  uint64_t epoch = 0;
+  int64_t n = 0;
+  hipError_t reserve(uint64_t rows) { return d_rows.reserve(rows * WORDS); }
+};
+
 // The access timeline (nmg_set_timeline): the cell array, the selected entries
 // in id order (their cells lie in that order; each entry's base and rows are
 // also in its DevEntry::pad1, tl_pad) and the getters' work arrays.
@@ -265,11 +279,9 @@ struct Timeline {
   DevBuf<uint32_t> d_cells;
   std::vector<uint32_t> ids, base, nrows;  // base has one more: ncells
   DevBuf<uint32_t> d_ids, d_base, d_nrows;
-  // rows of the current results epoch (nmg_count_timeline_cells, then the copy out)
-  DevBuf<uint32_t> d_cnt, d_rows;
+  RowSet<uint32_t, 5> rows;  // (entry, bin, thread, row, count)
+  DevBuf<uint32_t> d_cnt;    // their per-segment counts, offsets and the scan's partial sums
   DevBuf<uint64_t> d_off, d_part;
-  uint64_t rows_epoch = 0;
-  int64_t n = 0;
 };
 
 // The page cost cells (nmg_set_page_cost): one u64 array parallel to the page
@@ -282,11 +294,7 @@ struct PageCost {
   uint64_t budget = 0;             // bytes the array may take (opt.budget_bytes, or the default)
   uint32_t rounds = kCostRounds;   // Params::cost_rounds
   DevBuf<uint64_t> d_cells;        // [T * tab.cells()]; empty while the table has no dense cell
-  // rows of the current results epoch (nmg_count_cost_cells, then the copy
-  // out); the per-entry work arrays are cprep.lay's
-  DevBuf<uint64_t> d_rows;
-  uint64_t rows_epoch = 0;
-  int64_t n = 0;
+  RowSet<uint64_t, 4> rows;        // (entry, thread, page, value); the per-entry work arrays are cprep.lay's
 };
 
 // NUMA placement (nmg_placement.hip): groups on the device (PlaceParams'
@@ -314,13 +322,10 @@ struct PlaceState {
   DevBuf<uint32_t> d_tnode, d_hflag, d_hpnode, d_hlnode;
   DevBuf<uint64_t> d_hkeys, d_hvals, d_hskeys, d_hsvals, d_hpcnt, d_hoff, d_hpart, d_hgfirst, d_hn;
   DevBuf<uint8_t> d_htmp;
-  // nmg_count_object_blocks, then the copy out: rows of this epoch and these options
-  DevBuf<uint64_t> d_rows;
-  uint64_t rows_epoch = 0;
+  RowSet<uint64_t, 5> rows;  // (entry, node, start, end, count), made for the options below: others clear rows.epoch
   uint32_t N = 0, D = 0;
   uint64_t source = 0;  // nmg_placement_options::source of those rows
   std::vector<uint32_t> node;  // the thread -> node map of those rows (PlaceMap::node)
-  int64_t n = 0;
 };
 
 struct nmg_engine {
@@ -340,10 +345,9 @@ struct nmg_engine {
 
   // object table
   bool have_table = false;
-  // results epoch: bumped by every call that can change a counter; the page
-  // cells counted by nmg_count_page_cells stay on the device (cprep.d_rows)
-  // until nmg_get_page_cells of the same epoch copies them out
-  uint64_t epoch = 1, cells_epoch = 0;
+  // results epoch: bumped by every call that can change a counter; the row
+  // sets (RowSet) prepared in one are served until the next
+  uint64_t epoch = 1;
   // the counter arrays hold what the last reset wrote (no analysis, import or
   // table update since): the local pass may store instead of adding
   bool counters_fresh = false;
@@ -378,8 +382,7 @@ struct nmg_engine {
   // the synchronous page-cell getters' state (cells_prepare), kept across calls
   struct CellsPrep {
     CellLayout lay;
-    DevBuf<uint4> d_rows;  // [n] dense rows, on the device until copied out
-    int64_t n = 0;         // rows, dense and sparse
+    RowSet<uint32_t, 4> rows;  // (entry, thread, page, count): n dense and sparse rows, the dense ones on the device
     // the sparse table's cells as downloaded ((key, count) words), the sparse
     // entries of that table and their first rows: placed by cells_fill
     std::vector<uint64_t> sparse_kv, soff;
@@ -591,17 +594,26 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job);
 int route_settle(nmg_engine* h);
 int decode_error_word(nmg_engine* h, uint64_t w);
 int cells_prepare(nmg_engine* h);
-int cells_fill(nmg_engine* h, uint32_t* rows);
-int collect_page_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);
-struct WalkCounters {  // walk_counters' arrays (empty while the walk order is the id order)
-  std::vector<uint64_t> size, first, cw;
-  std::vector<uint32_t> pos;
-};
-int walk_counters(nmg_engine* h, const HostResults& r, nmg_host_results& res, WalkCounters& w);
+int cells_fill(nmg_engine* h, const RowSet<uint32_t, 4>& s, uint32_t* rows);  // rows_get's fill for the page cells
 int timeline_prepare(nmg_engine* h);
 int cost_prepare(nmg_engine* h);
-int collect_cost_cells(nmg_engine* h, std::vector<uint64_t>* rows, int64_t* count);  // [n][4]
-int collect_timeline_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count);  // [n][5]
+// What a report has before its rows: the counters downloaded, and res zeroed
+// but for nb_threads, match_samples = 1 and what the call-site registry reads
+// per entry, in the report's walk order (nmg_walk_order.h; meta follows it).
+struct ReportInput { HostResults r; nmg_host_results res; WalkCounters w; };
+int report_begin(nmg_engine* h, ReportInput& in);
+// cnt[n] scanned into off[n + 1] and the total read back: the one host wait of
+// a prepare before its emit; `also` enqueues what else the wait should cover.
+inline hipError_t scan_nothing() { return hipSuccess; }
+template <class Also = hipError_t (*)()>
+int scan_total(nmg_engine* h, const uint32_t* cnt, uint64_t n, uint64_t* off, uint64_t* part, uint64_t* total,
+               Also also = scan_nothing) {
+  HIP_TRY(h, launch_scan_u32(h->stream, cnt, n, off, part));
+  HIP_TRY(h, hipMemcpyAsync(total, off + n, 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, also());
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return NMG_OK;
+}
 void* array_ptr(nmg_engine* h, int which, size_t* bytes);
 int scratch_u64(nmg_engine* h);
 int sparse_nonempty(nmg_engine* h, bool* out);
@@ -612,3 +624,41 @@ int multi_analyze(nmg_engine* h);
 int multi_finish(nmg_engine* h);
 int multi_buffer_found(nmg_engine* h, std::vector<uint32_t>& nf);
 #pragma GCC visibility pop
+
+// ---- row sets: prepare(h) leaves s.n rows of the current results epoch in
+// s.d_rows, or fails; it runs once per epoch, whichever call comes first
+template <class RS, class Prepare>
+int rows_prepare(nmg_engine* h, RS& s, Prepare&& prepare) {
+  if (s.epoch == h->epoch) return NMG_OK;
+  s.epoch = 0;
+  const int rc = prepare(h);
+  if (!rc) s.epoch = h->epoch;
+  return rc;
+}
+template <class RS, class Prepare>
+int64_t rows_count(nmg_engine* h, RS& s, Prepare&& prepare) {
+  const int rc = rows_prepare(h, s, prepare);
+  return rc ? rc : s.n;
+}
+// the prepared rows, device to host: the `fill` of every product but the page cells (cells_fill)
+struct RowsCopy {
+  template <class RS>
+  int operator()(nmg_engine* h, const RS& s, typename RS::word* rows) const {
+    if (s.n) HIP_TRY(h, hipMemcpy(rows, s.d_rows, (size_t)s.n * RS::kWords * sizeof(*rows), hipMemcpyDeviceToHost));
+    return NMG_OK;
+  }
+};
+template <class RS, class Prepare, class Fill = RowsCopy>
+int rows_get(nmg_engine* h, RS& s, Prepare&& prepare, typename RS::word* rows, int64_t n, Fill fill = Fill()) {
+  const int rc = rows_prepare(h, s, prepare);
+  if (rc) return rc;
+  if (s.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
+  return n ? fill(h, s, rows) : NMG_OK;
+}
+template <class RS, class Prepare, class Fill = RowsCopy>
+int rows_collect(nmg_engine* h, RS& s, Prepare&& prepare, std::vector<typename RS::word>* rows, Fill fill = Fill()) {
+  const int rc = rows_prepare(h, s, prepare);
+  if (rc) return rc;
+  rows->resize((size_t)s.n * RS::kWords);
+  return fill(h, s, rows->data());
+}

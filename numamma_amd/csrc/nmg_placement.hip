@@ -11,6 +11,7 @@
 #include "nmg_engine_impl.h"
 
 #include <rocprim/device/device_radix_sort.hpp>  // (after <cstring>; this translation unit only)
+#include <tuple>
 
 namespace nmg {
 
@@ -505,10 +506,9 @@ int run_huge(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, const PlaceP
   HIP_TRY(h, S.d_htmp.reserve(tmp_bytes));
   HIP_TRY(h, launch_place_huge_sort(st, q, n, S.d_htmp, tmp_bytes));
   HIP_TRY(h, launch_place_huge_reduce(st, q, n));
-  HIP_TRY(h, launch_scan_u32(st, S.d_hflag, n, S.d_hoff, S.d_hpart));
   uint64_t nq = 0;
-  HIP_TRY(h, hipMemcpyAsync(&nq, S.d_hoff + n, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(h, hipStreamSynchronize(st));
+  rc = scan_total(h, S.d_hflag, n, S.d_hoff, S.d_hpart, &nq);
+  if (rc) return rc;
   if (!nq) return NMG_OK;
   HIP_TRY(h, launch_place_huge_compact(st, q, n));
   HIP_TRY(h, launch_place_huge_starts(st, q, nq));
@@ -519,10 +519,9 @@ int run_huge(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, const PlaceP
   return NMG_OK;
 }
 
-// fold, count, scan, emit over the groups d: *n rows left in d_rows
-int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, bool from_cost, DevBuf<uint64_t>& d_rows,
-               int64_t* n) {
-  *n = 0;
+// fold, count, scan, emit over the groups d: rows.n rows left in rows.d_rows
+int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, bool from_cost, RowSet<uint64_t, 5>& rows) {
+  rows.n = 0;
   if (!d.G) return NMG_OK;
   PlaceState& S = h->place;
   hipStream_t st = h->stream;
@@ -559,20 +558,19 @@ int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, bool from_
     const int rc = run_huge(h, d, map, p, q, &m);
     if (rc) return rc;
   }
-  HIP_TRY(h, launch_scan_u32(st, S.d_bcnt, d.G, S.d_boff, S.d_part));
   uint64_t nrows = 0;
-  HIP_TRY(h, hipMemcpyAsync(&nrows, S.d_boff + d.G, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(h, hipStreamSynchronize(st));  // (also: the thread map's vectors were read)
+  const int rc = scan_total(h, S.d_bcnt, d.G, S.d_boff, S.d_part, &nrows);  // (its wait also: the thread map's vectors were read)
+  if (rc) return rc;
   if (nrows) {
-    HIP_TRY(h, d_rows.reserve(nrows * 5));
-    HIP_TRY(h, hipMemsetAsync(d_rows, 0, nrows * 40, st));
-    p.rows = d_rows;
+    HIP_TRY(h, rows.reserve(nrows));
+    HIP_TRY(h, hipMemsetAsync(rows.d_rows, 0, nrows * 40, st));
+    p.rows = rows.d_rows;
     HIP_TRY(h, launch_place_emit(st, p));
-    q.rows = d_rows;
+    q.rows = rows.d_rows;
     HIP_TRY(h, launch_place_huge_emit(st, q, m));
     HIP_TRY(h, hipStreamSynchronize(st));
   }
-  *n = (int64_t)nrows;
+  rows.n = (int64_t)nrows;
   return NMG_OK;
 }
 
@@ -590,14 +588,9 @@ int placement_begin(nmg_engine* h, const nmg_placement_options* p, PlaceMap& map
   return nmg_synchronize(h);
 }
 
-// the object blocks of the current results epoch and of p, left in place.d_rows
-int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p) {
-  PlaceMap map;
-  int rc = placement_begin(h, p, map);
-  if (rc) return rc;
+// the object blocks of the current results epoch and of p, left in place.rows
+int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p, const PlaceMap& map) {
   PlaceState& S = h->place;
-  if (S.rows_epoch == h->epoch && S.N == map.N && S.D == map.D && S.source == p->source && S.node == map.node)
-    return NMG_OK;
   const bool huge = (p->source & NMG_PLACE_HUGE) != 0;
   if (S.obj_dirty || S.obj_huge != huge) {  // (the table's groups: uploaded once per table and flag)
     std::vector<uint64_t> npages, base;
@@ -607,20 +600,27 @@ int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p) {
     PlaceGroups g;
     placement_object_groups(h->E, npages.data(), dense.data(), g, huge);
     S.obj_dirty = true;
-    rc = upload_groups(h, S.obj, g, base, ids);
+    const int rc = upload_groups(h, S.obj, g, base, ids);
     if (rc) return rc;
     S.obj_dirty = false;
     S.obj_huge = huge;
   }
-  S.rows_epoch = 0;
-  rc = run_blocks(h, S.obj, map, p->source == NMG_PLACE_PAGE_COST, S.d_rows, &S.n);
+  return run_blocks(h, S.obj, map, p->source == NMG_PLACE_PAGE_COST, S.rows);
+}
+
+// nmg_count_object_blocks (n null) and nmg_get_object_blocks: the options
+// checked, the row set made stale if it was prepared for others, then the rows
+int64_t object_blocks(nmg_engine* h, const nmg_placement_options* p, uint64_t* rows, const int64_t* n) {
+  PlaceMap map;
+  const int rc = placement_begin(h, p, map);
   if (rc) return rc;
-  S.rows_epoch = h->epoch;
-  S.N = map.N;
-  S.D = map.D;
-  S.source = p->source;
-  S.node = map.node;
-  return NMG_OK;
+  PlaceState& S = h->place;
+  if (std::tie(S.N, S.D, S.source, S.node) != std::tie(map.N, map.D, p->source, map.node)) {
+    S.rows.epoch = 0;
+    std::tie(S.N, S.D, S.source, S.node) = std::tie(map.N, map.D, p->source, map.node);
+  }
+  auto prepare = [&](nmg_engine*) { return object_blocks_prepare(h, p, map); };
+  return n ? rows_get(h, S.rows, prepare, rows, *n) : rows_count(h, S.rows, prepare);
 }
 
 }  // namespace
@@ -628,18 +628,13 @@ int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p) {
 extern "C" int64_t nmg_count_object_blocks(nmg_engine* h, const nmg_placement_options* p) {
   if (!h || !p) return NMG_ERR_INVALID;
   Range range("nmg_count_object_blocks");
-  const int rc = object_blocks_prepare(h, p);
-  return rc ? rc : h->place.n;
+  return object_blocks(h, p, nullptr, nullptr);
 }
 
 extern "C" int nmg_get_object_blocks(nmg_engine* h, const nmg_placement_options* p, uint64_t* rows, int64_t n) {
   if (!h || !p || (n && !rows)) return NMG_ERR_INVALID;
   Range range("nmg_get_object_blocks");
-  const int rc = object_blocks_prepare(h, p);
-  if (rc) return rc;
-  if (h->place.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
-  if (n) HIP_TRY(h, hipMemcpy(rows, h->place.d_rows, (size_t)n * 40, hipMemcpyDeviceToHost));
-  return NMG_OK;
+  return (int)object_blocks(h, p, rows, &n);
 }
 
 // The call-site registry from the per-entry counters (as nmg_report builds
@@ -653,15 +648,8 @@ extern "C" int nmg_report_placement(nmg_engine* h, const nmg_object_meta* meta, 
   PlaceMap map;
   int rc = placement_begin(h, p, map);
   if (rc) return rc;
-  HostResults r;
-  rc = engine_download(h, r, true, false);
-  if (rc) return rc;
-  nmg_host_results res;
-  memset(&res, 0, sizeof(res));
-  res.nb_threads = h->T;
-  res.match_samples = 1;
-  WalkCounters w;  // (live online tables: meta follows the walk order)
-  rc = walk_counters(h, r, res, w);
+  ReportInput in;  // (live online tables: meta follows the walk order)
+  rc = report_begin(h, in);
   if (rc) return rc;
   std::vector<uint64_t> npages, base;
   std::vector<uint8_t> dense;
@@ -672,19 +660,17 @@ extern "C" int nmg_report_placement(nmg_engine* h, const nmg_object_meta* meta, 
   PlaceGroups g;
   std::vector<PlaceSite> sites;
   std::string err;
-  rc = placement_site_groups(&res, meta, opts && opts->online, npages.data(), dense.data(), g, sites, err,
+  rc = placement_site_groups(&in.res, meta, opts && opts->online, npages.data(), dense.data(), g, sites, err,
                              (p->source & NMG_PLACE_HUGE) != 0);
   std::vector<uint64_t> rows;
   if (!rc) {
     PlaceDev d;
-    DevBuf<uint64_t> d_rows;
-    int64_t n = 0;
+    RowSet<uint64_t, 5> set;  // (this call's own: the sites' blocks are not kept)
     rc = upload_groups(h, d, g, base, ids);
-    if (!rc) rc = run_blocks(h, d, map, p->source == NMG_PLACE_PAGE_COST, d_rows, &n);
+    if (!rc)
+      rc = rows_collect(h, set, [&](nmg_engine*) { return run_blocks(h, d, map, p->source == NMG_PLACE_PAGE_COST, set); }, &rows);
     if (rc) return rc;
-    rows.resize((size_t)n * 5);
-    if (n) HIP_TRY(h, hipMemcpy(rows.data(), d_rows, (size_t)n * 40, hipMemcpyDeviceToHost));
-    rc = write_blocks(sites, rows.data(), n, opts, err);
+    rc = write_blocks(sites, rows.data(), set.n, opts, err);
   }
   if (rc && !err.empty()) h->last_error = err;
   return rc;

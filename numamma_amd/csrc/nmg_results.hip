@@ -137,7 +137,7 @@ extern "C" int nmg_get_object_levels(nmg_engine* h, uint64_t* levels) {
 
 
 // ---- the table's page-cell layout, shared by the synchronous getters
-// (cells_prepare / cells_fill) and the results snapshot
+// (dense_rows / cells_fill) and the results snapshot
 
 int CellLayout::ensure(nmg_engine* h, uint64_t newE, uint64_t new_nsent) {
   if (newE != E || !d_cnt) {  // (d_cnt: the last one allocated)
@@ -222,37 +222,75 @@ static int cprep_layout(nmg_engine* h) {
   return NMG_OK;
 }
 
-// Every non-zero (entry, thread, page) cell, entries in id order, each
-// entry's cells in (thread, page) order.  On the device, in buffers kept
-// across calls (the table's cell layout uploaded once per table): dense cells
-// counted per entry (cells_count), the sparse table's cells (entries past the
-// dense budget, e.g. [stack]) counted per entry from its compacted slots, an
-// exclusive scan into row offsets, the dense rows emitted (cells_emit).  The
-// rows stay on the device (cprep.d_rows) until copied out, so only they cross
-// PCIe, once; the sparse rows are sorted on the host and placed at their
-// entries' offsets.  Cached per results epoch: nmg_count_page_cells then
-// nmg_get_page_cells does the work once.
-int cells_prepare(nmg_engine* h) {
-  if (h->cells_epoch == h->epoch) return NMG_OK;
-  const bool timing = getenv("NMG_CELLS_TIMING") != nullptr;  // (phase times on stderr)
-  auto tp = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
+struct Lap {  // NMG_CELLS_TIMING: the page cells' phase times on stderr
+  bool on;
+  std::chrono::steady_clock::time_point tp = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "cells_prepare: %-10s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tp).count());
+    if (on) fprintf(stderr, "cells_prepare: %-10s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tp).count());
     tp = now;
-  };
+  }
+};
+
+// (launch_cells_emit writes a page-cell row as one uint4)
+static uint4* emit_rows(uint32_t* rows) { return reinterpret_cast<uint4*>(rows); }
+static uint64_t* emit_rows(uint64_t* rows) { return rows; }
+
+// The dense rows of `cells` (the page histogram, or the cost cells at its
+// index; null: no dense cell) over cprep's layout and work arrays: counted per
+// entry, scanned into row offsets, emitted into s.d_rows.  with_sparse (page
+// cells only): the sparse table's entries are counted too, from the slots
+// sparse_download left in d_sparse_ck, and their first rows read back into
+// cprep.soff for cells_fill.  A pass ends before it returns, so the page
+// cells' and the cost cells' passes share the work arrays without meeting.
+template <class CELL, class RS>
+static int dense_rows(nmg_engine* h, const CELL* cells, RS& s, bool with_sparse, Lap lap) {
+  const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
+  CellLayout& C = h->cprep.lay;
+  uint64_t n = 0;
+  if (E) {
+    hipStream_t st = h->stream;
+    if (cells)
+      HIP_TRY(h, launch_cells_count(st, cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
+    else
+      HIP_TRY(h, hipMemsetAsync(C.d_cnt, 0, E * 4, st));
+    if (with_sparse)
+      HIP_TRY(h, launch_cells_sparse_count(st, h->cnt.d_sparse_ck,
+                                           reinterpret_cast<const unsigned long long*>(h->cnt.d_sparse_ck + 2 * h->sparse_cap),
+                                           h->sparse_cap, C.d_sent, (uint32_t)nsent, C.d_base, C.d_cnt));
+    const int rc = scan_total(h, C.d_cnt, E, C.d_off, C.d_part, &n, [&]() -> hipError_t {
+      if (!with_sparse) return hipSuccess;
+      const hipError_t e = launch_gather_off(st, C.d_off, C.d_sent, (uint32_t)nsent, C.d_soff);
+      return e != hipSuccess ? e : hipMemcpyAsync(h->cprep.soff.data(), C.d_soff, nsent * 8, hipMemcpyDeviceToHost, st);
+    });
+    if (rc) return rc;
+    lap("count");
+    if (cells && n) {
+      HIP_TRY(h, s.reserve(n));
+      HIP_TRY(h, launch_cells_emit(st, cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off,
+                                   emit_rows(s.d_rows.get())));
+      HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    lap("emit");
+  }
+  s.n = (int64_t)n;
+  return NMG_OK;
+}
+
+// Every non-zero (entry, thread, page) cell, entries in id order, each
+// entry's cells in (thread, page) order: the dense rows stay on the device
+// until copied out, so only they cross PCIe, once; the sparse table's cells
+// (entries past the dense budget, e.g. [stack]) are downloaded compacted and
+// placed at their entries' offsets by cells_fill.
+int cells_prepare(nmg_engine* h) {
+  Lap lap{getenv("NMG_CELLS_TIMING") != nullptr};
   int rc = nmg_synchronize(h);
   if (rc) return rc;
   lap("sync");
-  const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   auto& P = h->cprep;
-  CellLayout& C = P.lay;
   rc = cprep_layout(h);
   if (rc) return rc;
   lap("meta");
-  // sparse cells: compacted on the device (sparse_download, which leaves
-  // them in d_sparse_ck); cells_fill places their rows
   std::vector<uint64_t> k;
   std::vector<uint32_t> v;
   rc = sparse_download(h, k, v);
@@ -263,139 +301,66 @@ int cells_prepare(nmg_engine* h) {
     P.sparse_kv[2 * i + 1] = v[i];
   }
   lap("sparse");
-  const bool dense = h->tab.cells() && E;
-  uint64_t n = 0;
-  std::vector<uint64_t>& soff = P.soff;
-  soff.assign(nsent, 0);
-  if (E) {
-    hipStream_t st = h->stream;
-    if (dense)
-      HIP_TRY(h, launch_cells_count(st, h->cnt.d_hist, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
-    else
-      HIP_TRY(h, hipMemsetAsync(C.d_cnt, 0, E * 4, st));
-    if (!k.empty())
-      HIP_TRY(h, launch_cells_sparse_count(st, h->cnt.d_sparse_ck,
-                                           reinterpret_cast<const unsigned long long*>(h->cnt.d_sparse_ck + 2 * h->sparse_cap),
-                                           h->sparse_cap, C.d_sent, (uint32_t)nsent, C.d_base, C.d_cnt));
-    HIP_TRY(h, launch_scan_u32(st, C.d_cnt, E, C.d_off, C.d_part));
-    HIP_TRY(h, hipMemcpyAsync(&n, C.d_off + E, 8, hipMemcpyDeviceToHost, st));
-    if (!k.empty()) {
-      HIP_TRY(h, launch_gather_off(st, C.d_off, C.d_sent, (uint32_t)nsent, C.d_soff));
-      HIP_TRY(h, hipMemcpyAsync(soff.data(), C.d_soff, nsent * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(h, hipStreamSynchronize(st));
-    lap("count");
-    if (dense && n) {
-      HIP_TRY(h, P.d_rows.reserve(n));
-      HIP_TRY(h, launch_cells_emit(st, h->cnt.d_hist, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off, P.d_rows));
-      HIP_TRY(h, hipStreamSynchronize(st));
-    }
-    lap("emit");
-  }
-  if (timing) fprintf(stderr, "cells_prepare: %llu rows\n", (unsigned long long)n);
-  P.n = (int64_t)n;
-  h->cells_epoch = h->epoch;
+  P.soff.assign(h->tab.sparse_entries.size(), 0);
+  rc = dense_rows(h, h->tab.cells() && h->E ? h->cnt.d_hist.get() : nullptr, P.rows, !k.empty(), lap);
+  if (rc) return rc;
+  if (lap.on) fprintf(stderr, "cells_prepare: %llu rows\n", (unsigned long long)P.rows.n);
   return NMG_OK;
 }
 
-// ---- page cost rows: the page cells' count / scan / emit over the u64 array
-// (same index, so cprep's layout and per-entry work arrays serve; a pass ends
-// before it returns, so the two do not meet).  The rows stay on the device
-// (cost.d_rows) until copied out, cached per results epoch -- the options are
-// the cells' own: nmg_set_page_cost bumps the epoch.
-int cost_prepare(nmg_engine* h) {
-  PageCost& c = h->cost;
-  if (!c.on) return fail(h, NMG_ERR_STATE, "no page cost cells set (nmg_set_page_cost)");
-  if (c.rows_epoch == h->epoch) return NMG_OK;
-  int rc = nmg_synchronize(h);
-  if (rc) return rc;
-  rc = cprep_layout(h);
-  if (rc) return rc;
-  CellLayout& C = h->cprep.lay;
-  const uint64_t E = h->E;
-  uint64_t n = 0;
-  if (E && c.d_cells) {
-    hipStream_t st = h->stream;
-    HIP_TRY(h, launch_cells_count(st, c.d_cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
-    HIP_TRY(h, launch_scan_u32(st, C.d_cnt, E, C.d_off, C.d_part));
-    HIP_TRY(h, hipMemcpyAsync(&n, C.d_off + E, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    if (n) {
-      HIP_TRY(h, c.d_rows.reserve(n * 4));
-      HIP_TRY(h, launch_cells_emit(st, c.d_cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off, c.d_rows));
-      HIP_TRY(h, hipStreamSynchronize(st));
-    }
-  }
-  c.n = (int64_t)n;
-  c.rows_epoch = h->epoch;
-  return NMG_OK;
-}
-
-int collect_cost_cells(nmg_engine* h, std::vector<uint64_t>* rows, int64_t* count) {
-  int rc = cost_prepare(h);
-  if (rc) return rc;
-  *count = h->cost.n;
-  rows->resize((size_t)h->cost.n * 4);
-  if (h->cost.n) HIP_TRY(h, hipMemcpy(rows->data(), h->cost.d_rows, (size_t)h->cost.n * 32, hipMemcpyDeviceToHost));
-  return NMG_OK;
-}
-
-extern "C" int64_t nmg_count_cost_cells(nmg_engine* h) {
-  if (!h) return NMG_ERR_INVALID;
-  int rc = cost_prepare(h);
-  return rc ? rc : h->cost.n;
-}
-
-extern "C" int nmg_get_cost_cells(nmg_engine* h, uint64_t* rows, int64_t n) {
-  if (!h || (n && !rows)) return NMG_ERR_INVALID;
-  int rc = cost_prepare(h);
-  if (rc) return rc;
-  if (h->cost.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
-  if (n) HIP_TRY(h, hipMemcpy(rows, h->cost.d_rows, (size_t)n * 32, hipMemcpyDeviceToHost));
-  return NMG_OK;
-}
-
-// the prepared rows into rows[cprep.n * 4]: dense rows D2H, sparse rows placed
-int cells_fill(nmg_engine* h, uint32_t* rows) {
-  const bool dense = h->tab.cells() && h->E;
+// rows[s.n * 4]: dense rows D2H (none where the table has no dense cell), sparse rows placed
+int cells_fill(nmg_engine* h, const RowSet<uint32_t, 4>& s, uint32_t* rows) {
   const auto t0 = std::chrono::steady_clock::now();
   const auto& P = h->cprep;
-  if (dense && P.n) HIP_TRY(h, hipMemcpy(rows, P.d_rows, (size_t)P.n * 16, hipMemcpyDeviceToHost));
+  if (h->tab.cells() && h->E) {
+    const int rc = RowsCopy()(h, s, rows);
+    if (rc) return rc;
+  }
   if (getenv("NMG_CELLS_TIMING"))
     fprintf(stderr, "cells_fill: rows D2H %.3f ms\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   place_sparse_rows(P.sparse_kv.data(), P.sparse_kv.size() / 2, P.sent_entry, P.soff.data(), rows);
   return NMG_OK;
 }
-int collect_page_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count) {
-  int rc = cells_prepare(h);
-  if (rc) return rc;
-  *count = h->cprep.n;
-  rows->resize((size_t)h->cprep.n * 4);
-  return cells_fill(h, rows->data());
-}
 
 extern "C" int64_t nmg_count_page_cells(nmg_engine* h) {
   if (!h || !h->have_table) return NMG_ERR_INVALID;
-  int rc = cells_prepare(h);
-  return rc ? rc : h->cprep.n;
+  return rows_count(h, h->cprep.rows, cells_prepare);
 }
 
 extern "C" int nmg_get_page_cells(nmg_engine* h, uint32_t* rows, int64_t n) {
   if (!h || !h->have_table || (n && !rows)) return NMG_ERR_INVALID;
-  int rc = cells_prepare(h);
+  return rows_get(h, h->cprep.rows, cells_prepare, rows, n, cells_fill);
+}
+
+// ---- page cost rows: the dense rows of the u64 array (the options are the
+// cells' own: nmg_set_page_cost bumps the epoch)
+int cost_prepare(nmg_engine* h) {
+  PageCost& c = h->cost;
+  if (!c.on) return fail(h, NMG_ERR_STATE, "no page cost cells set (nmg_set_page_cost)");
+  int rc = nmg_synchronize(h);
   if (rc) return rc;
-  if (h->cprep.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
-  return n ? cells_fill(h, rows) : NMG_OK;
+  rc = cprep_layout(h);
+  if (rc) return rc;
+  c.rows.n = 0;
+  return c.d_cells ? dense_rows(h, c.d_cells.get(), c.rows, false, Lap{false}) : NMG_OK;
+}
+
+extern "C" int64_t nmg_count_cost_cells(nmg_engine* h) {
+  if (!h) return NMG_ERR_INVALID;
+  return rows_count(h, h->cost.rows, cost_prepare);
+}
+
+extern "C" int nmg_get_cost_cells(nmg_engine* h, uint64_t* rows, int64_t n) {
+  if (!h || (n && !rows)) return NMG_ERR_INVALID;
+  return rows_get(h, h->cost.rows, cost_prepare, rows, n);
 }
 
 // ---- access timeline rows: counted per segment, scanned and emitted on the
-// device (the page cells' pattern); they stay there (tl.d_rows) until copied
-// out, cached per results epoch
+// device (the page cells' pattern)
 int timeline_prepare(nmg_engine* h) {
   Timeline& t = h->tl;
   if (!t.on) return fail(h, NMG_ERR_STATE, "no timeline set (nmg_set_timeline)");
-  if (t.rows_epoch == h->epoch) return NMG_OK;
   int rc = nmg_synchronize(h);
   if (rc) return rc;
   uint64_t n = 0;
@@ -406,43 +371,27 @@ int timeline_prepare(nmg_engine* h) {
     HIP_TRY(h, t.d_off.reserve(nseg + 1));
     HIP_TRY(h, t.d_part.reserve(scan_parts(nseg) + 1));
     HIP_TRY(h, launch_tl_count(st, t.d_cells, t.ncells, t.d_cnt));
-    HIP_TRY(h, launch_scan_u32(st, t.d_cnt, nseg, t.d_off, t.d_part));
-    HIP_TRY(h, hipMemcpyAsync(&n, t.d_off + nseg, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
+    rc = scan_total(h, t.d_cnt, nseg, t.d_off, t.d_part, &n);
+    if (rc) return rc;
     if (n) {
-      HIP_TRY(h, t.d_rows.reserve(n * 5));
+      HIP_TRY(h, t.rows.reserve(n));
       HIP_TRY(h, launch_tl_emit(st, t.d_cells, t.ncells, t.d_ids, t.d_base, t.d_nrows, (uint32_t)t.ids.size(), h->T,
-                                t.d_off, t.d_rows));
+                                t.d_off, t.rows.d_rows));
       HIP_TRY(h, hipStreamSynchronize(st));
     }
   }
-  t.n = (int64_t)n;
-  t.rows_epoch = h->epoch;
-  return NMG_OK;
-}
-
-int collect_timeline_cells(nmg_engine* h, std::vector<uint32_t>* rows, int64_t* count) {
-  int rc = timeline_prepare(h);
-  if (rc) return rc;
-  *count = h->tl.n;
-  rows->resize((size_t)h->tl.n * 5);
-  if (h->tl.n) HIP_TRY(h, hipMemcpy(rows->data(), h->tl.d_rows, (size_t)h->tl.n * 20, hipMemcpyDeviceToHost));
+  t.rows.n = (int64_t)n;
   return NMG_OK;
 }
 
 extern "C" int64_t nmg_count_timeline_cells(nmg_engine* h) {
   if (!h) return NMG_ERR_INVALID;
-  int rc = timeline_prepare(h);
-  return rc ? rc : h->tl.n;
+  return rows_count(h, h->tl.rows, timeline_prepare);
 }
 
 extern "C" int nmg_get_timeline_cells(nmg_engine* h, uint32_t* rows, int64_t n) {
   if (!h || (n && !rows)) return NMG_ERR_INVALID;
-  int rc = timeline_prepare(h);
-  if (rc) return rc;
-  if (h->tl.n != n) return fail(h, NMG_ERR_INVALID, "row count mismatch");
-  if (n) HIP_TRY(h, hipMemcpy(rows, h->tl.d_rows, (size_t)n * 20, hipMemcpyDeviceToHost));
-  return NMG_OK;
+  return rows_get(h, h->tl.rows, timeline_prepare, rows, n);
 }
 
 // ---- multi-GPU merge support

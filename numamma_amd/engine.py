@@ -284,12 +284,15 @@ class Engine:
         self._c(lib.nmg_get_object_levels(self.h, _ptr(lv, C.c_uint64)))
         return lv
 
-    def page_cells(self) -> np.ndarray:
-        n = lib.nmg_count_page_cells(self.h)
-        self._c(n)
-        rows = np.empty((n, 4), dtype=np.uint32)  # (every row written by the engine)
-        self._c(lib.nmg_get_page_cells(self.h, _ptr(rows, C.c_uint32), n))
+    def _rows(self, count, get, width: int, dtype, *args) -> np.ndarray:
+        """A row set: count(h, *args) prepares the rows, get(h, *args, rows, n) copies them out."""
+        n = self._c(count(self.h, *args))
+        rows = np.empty((n, width), dtype=dtype)  # (every row written by the engine)
+        self._c(get(self.h, *args, _ptr(rows, C.c_uint32 if dtype == np.uint32 else C.c_uint64), n))
         return rows
+
+    def page_cells(self) -> np.ndarray:
+        return self._rows(lib.nmg_count_page_cells, lib.nmg_get_page_cells, 4, np.uint32)
 
     def results_begin(self):
         """nmg_results_begin: the results so far snapshotted on the device and
@@ -346,11 +349,7 @@ class Engine:
     def timeline_cells(self) -> np.ndarray:
         """The non-zero timeline cells as (entry, bin, thread, row, count) rows,
         sorted by (entry, bin, thread, row)."""
-        n = lib.nmg_count_timeline_cells(self.h)
-        self._c(n)
-        rows = np.empty((n, 5), dtype=np.uint32)  # (every row written by the engine)
-        self._c(lib.nmg_get_timeline_cells(self.h, _ptr(rows, C.c_uint32), n))
-        return rows
+        return self._rows(lib.nmg_count_timeline_cells, lib.nmg_get_timeline_cells, 5, np.uint32)
 
     def report_timeline(self, output_dir: str, online: bool = False):
         """nmg_report_timeline: callsite_timeline_<id>.dat per call site."""
@@ -375,11 +374,7 @@ class Engine:
     def cost_cells(self) -> np.ndarray:
         """The non-zero cost cells as u64 (entry, thread, page, value) rows,
         sorted by (entry, thread, page)."""
-        n = lib.nmg_count_cost_cells(self.h)
-        self._c(n)
-        rows = np.empty((n, 4), dtype=np.uint64)  # (every row written by the engine)
-        self._c(lib.nmg_get_cost_cells(self.h, _ptr(rows, C.c_uint64), n))
-        return rows
+        return self._rows(lib.nmg_count_cost_cells, lib.nmg_get_cost_cells, 4, np.uint64)
 
     def report_page_cost(self, output_dir: str, online: bool = False):
         """nmg_report_page_cost: callsite_cost_<id>.dat per call site."""
@@ -401,10 +396,7 @@ class Engine:
         NMG_PLACE_HUGE: every object, the ones with sparse page cells
         ([stack], arrays past the dense cap or the histogram budget) included."""
         po, keep = _lib.placement_options(self.nb_threads, nb_nodes, thread_node, density_threshold, source=source)
-        n = lib.nmg_count_object_blocks(self.h, C.byref(po))
-        self._c(n)
-        rows = np.empty((n, 5), dtype=np.uint64)  # (every row written by the engine)
-        self._c(lib.nmg_get_object_blocks(self.h, C.byref(po), _ptr(rows, C.c_uint64), n))
+        rows = self._rows(lib.nmg_count_object_blocks, lib.nmg_get_object_blocks, 5, np.uint64, C.byref(po))
         del keep
         return rows
 
