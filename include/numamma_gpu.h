@@ -382,7 +382,8 @@ int nmg_get_timeline_cells(nmg_engine *h, uint32_t *rows /* [n][5] */, int64_t n
  * buffer_addr) / 4096) as the page histogram has it; a sample that hits
  * several selected buckets adds once.  Only entries with dense page cells
  * have cost cells (the timeline's and the placement's selection: huge ranges
- * such as [stack] have none).
+ * such as [stack] have none) -- unless the cells are set with
+ * nmg_set_page_cost_ex and scope NMG_COST_SCOPE_ALL, below.
  * nmg_set_page_cost allocates and zeroes the cells, cell (e, t, p) lying at
  * the page histogram's own index: after nmg_set_objects, on a single-GPU
  * engine created with NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST, with no stream
@@ -399,7 +400,32 @@ int nmg_get_timeline_cells(nmg_engine *h, uint32_t *rows /* [n][5] */, int64_t n
  * changes nothing).  The results snapshot does not hold them.
  * The getters (NMG_ERR_STATE without cost cells) return the non-zero cells as
  * (entry, thread, page, value) u64 rows in (entry, thread, page) order,
- * compacted on the device and cached per results epoch. */
+ * compacted on the device and cached per results epoch.
+ *
+ * The scope.  nmg_set_page_cost_ex(h, o, scope) is nmg_set_page_cost with the
+ * entries chosen: NMG_COST_SCOPE_DENSE is nmg_set_page_cost(h, o) itself;
+ * NMG_COST_SCOPE_ALL gives every entry cost cells, the sparse ones too --
+ * [stack], an entry of more than 2^24 page cells over all threads (a
+ * multi-GiB array), whatever hist_budget_bytes left sparse.  Any other scope
+ * is NMG_ERR_INVALID; every other precondition and error is that of
+ * nmg_set_page_cost.  The rule is unchanged but for its last sentence: a
+ * sparse entry's cell (e, t, p) is kept under its sparse index, t and the
+ * 32-bit page field -- the key under which its page count is kept
+ * (nmg_get_page_cells), one u64 per slot of the sparse page table.
+ * budget_bytes then covers the dense array plus 8 * sparse_capacity bytes,
+ * counted whenever the engine has a sparse page table, and when an
+ * nmg_update_objects brings the table's first sparse entry (past the budget
+ * that update fails with NMG_ERR_CAPACITY and changes nothing).  The getters
+ * return the dense and the sparse rows together in (entry, thread, page)
+ * order, as nmg_get_page_cells does, non-zero values only: a sparse cell with
+ * a count but no selected sample gives no row.  An entry that an online
+ * update turned from sparse to dense loses its sparse rows, as it loses its
+ * sparse page cells.  nmg_reset_counters zeroes the sparse cost cells with
+ * the sparse table; nmg_sparse_import rebuilds that table, so it zeroes them
+ * too: cost cells, dense or sparse, are not merged across ranks.  The
+ * placement folds the cells that exist (source NMG_PLACE_PAGE_COST, below),
+ * and nmg_report_page_cost gives a site its sparse members' cells too (stack
+ * sites stay skipped). */
 #define NMG_COST_COUNT 0
 #define NMG_COST_WEIGHT 1
 #define NMG_COST_NA 0x40000u                          /* bucket mask bit 18 */
@@ -413,6 +439,9 @@ struct nmg_page_cost_options {
   uint64_t budget_bytes; /* cap on the cell array (0: default 1 GiB) */
 };
 int nmg_set_page_cost(nmg_engine *h, const struct nmg_page_cost_options *o);
+#define NMG_COST_SCOPE_DENSE 0 /* nmg_set_page_cost: entries with dense page cells */
+#define NMG_COST_SCOPE_ALL 1   /* every entry: the sparse ones too */
+int nmg_set_page_cost_ex(nmg_engine *h, const struct nmg_page_cost_options *o, uint32_t scope);
 int64_t nmg_count_cost_cells(nmg_engine *h);
 int nmg_get_cost_cells(nmg_engine *h, uint64_t *rows /* [n][4] */, int64_t n);
 
@@ -658,7 +687,15 @@ int nmg_report_page_cost_host(const struct nmg_host_results *res, const struct n
  * place: "the page cell (e, t, p)" is then the cost cell, cnt and the rows'
  * count are cost sums, and density_threshold is compared with them.  The
  * rule, the rows and blocks.dat are otherwise the same.  The cached object
- * blocks are keyed by the source too.
+ * blocks are keyed by the source too.  It folds the cost cells that exist:
+ * which entries have them is chosen when the cells are set, not here.  On an
+ * engine whose cells were set with NMG_COST_SCOPE_ALL every member entry
+ * contributes, as under NMG_PLACE_HUGE below -- a sparse member through its
+ * sparse cost cell, a group with a sparse member computed from its touched
+ * pages alone, on the device -- and with NMG_COST_SCOPE_DENSE only the dense
+ * members do.  That is why NMG_PLACE_PAGE_COST | NMG_PLACE_HUGE stays
+ * refused: set the cells with NMG_COST_SCOPE_ALL and use NMG_PLACE_PAGE_COST.
+ * The cached object blocks are keyed by the scope too.
  *
  * NMG_PLACE_HUGE (a flag bit, with NMG_PLACE_PAGE_COUNTS only): every member
  * entry contributes, the sparse ones included -- entries of more than 2^24

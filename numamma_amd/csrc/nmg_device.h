@@ -171,20 +171,40 @@ __device__ __forceinline__ bool entry_match(uint4 a, uint4 b, uint64_t addr, uin
   return baddr <= addr && addr < bend && alloc <= ts && ts <= fr;
 }
 
-__device__ __forceinline__ void sparse_add(const Params& p, uint64_t key, uint64_t seq, uint32_t off, uint32_t cnt) {
-  *p.sparse_dirty = 1u;
+// The sparse page table's slot of `key`, inserted if absent; kNoSlot when the
+// table is full (a slot is below 2^31).  The lookup is the insert's CAS too:
+// a plain load of a key that another XCD inserted may be stale, and
+// CAS(~0, key) returning key is the lookup.
+constexpr uint32_t kNoSlot = ~0u;
+__device__ __forceinline__ uint32_t sparse_slot(const Params& p, uint64_t key) {
   uint64_t h = (key * 0x9E3779B97F4A7C15ull) >> 20;
   uint32_t slot = uint32_t(h) & p.sparse_mask;
   for (uint32_t probe = 0; probe <= p.sparse_mask; probe++) {
     unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(p.sparse_keys + slot),
                                         ~0ull, (unsigned long long)key);
-    if (prev == ~0ull || prev == key) {
-      atomicAdd(p.sparse_vals + slot, cnt);
-      return;
-    }
+    if (prev == ~0ull || prev == key) return slot;
     slot = (slot + 1) & p.sparse_mask;
   }
-  set_error(p, seq, off, kErrCapacity);
+  return kNoSlot;
+}
+
+// cnt more on the page count of `key`: sparse_slot plus the u32 add.  Its
+// slot, or kNoSlot with the error word set when the table is full.
+__device__ __forceinline__ uint32_t sparse_add(const Params& p, uint64_t key, uint64_t seq, uint32_t off, uint32_t cnt) {
+  *p.sparse_dirty = 1u;
+  const uint32_t slot = sparse_slot(p, key);
+  if (slot != kNoSlot) atomicAdd(p.sparse_vals + slot, cnt);
+  else set_error(p, seq, off, kErrCapacity);
+  return slot;
+}
+
+// The sparse cost cell (Params::sparse_cost) of the key at `slot`: the lane's
+// own no-return u64 add, no cross-lane step (sparse entries are the rare
+// path), so it may sit in a diverged region.  Every call follows a sparse_add
+// of the key -- it set the dirty flag, so the next reset clears this slot too.
+__device__ __forceinline__ void sparse_cost_add(const Params& p, uint32_t slot, uint64_t value) {
+  if (slot != kNoSlot && value)
+    atomicAdd(reinterpret_cast<unsigned long long*>(p.sparse_cost) + slot, (unsigned long long)value);
 }
 
 

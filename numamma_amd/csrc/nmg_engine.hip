@@ -261,6 +261,7 @@ extern "C" int nmg_reset_counters(nmg_engine* h) {
     // the one the analyses after it will set
     r.sparse_read = h->cnt.d_sparse_dirty + (h->nreset & 1);
     r.sparse_clear = h->cnt.d_sparse_dirty + ((h->nreset + 1) & 1);
+    r.sparse_cost = h->cost.on ? h->cost.d_sparse.get() : nullptr;  // (NMG_COST_SCOPE_ALL: cleared with the table)
   }
   // (a pending descriptor upload zeroes the per-buffer counts itself)
   if (h->d_bufcnt && (h->streaming || h->streamed || (!h->descs_dirty && !h->descs.empty()))) {
@@ -516,13 +517,13 @@ extern "C" int nmg_report(nmg_engine* h, const nmg_object_meta* meta, const nmg_
 
 // A row set and what the call-site registry needs (report_begin), handed to
 // a host writer that groups the rows by site: they go in any order.
-template <class RS, class Prepare, class Write>
-static int report_rows(nmg_engine* h, RS& s, Prepare prepare, Write write) {
+template <class RS, class Prepare, class Write, class Fill = RowsCopy>
+static int report_rows(nmg_engine* h, RS& s, Prepare prepare, Write write, Fill fill = Fill()) {
   ReportInput in;
   int rc = report_begin(h, in);
   if (rc) return rc;
   std::vector<typename RS::word> rows;
-  rc = rows_collect(h, s, prepare, &rows);
+  rc = rows_collect(h, s, prepare, &rows, fill);
   if (rc) return rc;
   walk_rewrite_entries(rows.data(), s.n, RS::kWords, in.w.pos);
   std::string err;
@@ -548,7 +549,7 @@ extern "C" int nmg_report_page_cost(nmg_engine* h, const nmg_object_meta* meta, 
   if (!h->cost.on) return fail(h, NMG_ERR_STATE, "no page cost cells set (nmg_set_page_cost)");
   return report_rows(h, h->cost.rows, cost_prepare, [&](const nmg_host_results* res, const uint64_t* rows, int64_t n, std::string& err) {
     return write_page_cost(res, meta, opts, rows, n, err);
-  });
+  }, cost_fill);
 }
 
 // Internal (not in include/numamma_gpu.h; bench.py): the first kernel's

@@ -295,6 +295,14 @@ struct PageCost {
   uint32_t rounds = kCostRounds;   // Params::cost_rounds
   DevBuf<uint64_t> d_cells;        // [T * tab.cells()]; empty while the table has no dense cell
   RowSet<uint64_t, 4> rows;        // (entry, thread, page, value); the per-entry work arrays are cprep.lay's
+  // NMG_COST_SCOPE_ALL: the sparse entries' cells, [sparse_cap] parallel to
+  // cnt.d_sparse_keys / d_sparse_vals -- the cost of a key at the slot the
+  // count table gave it; empty while the engine has no sparse page table.
+  // The rows then hold dense and sparse rows, the sparse ones placed by
+  // cost_fill from the compacted (key, cost) words and first rows kept here.
+  uint32_t scope = NMG_COST_SCOPE_DENSE;
+  DevBuf<uint64_t> d_sparse;
+  std::vector<uint64_t> sparse_kv, soff;
 };
 
 // NUMA placement (nmg_placement.hip): groups on the device (PlaceParams'
@@ -313,7 +321,8 @@ struct PlaceDev {
 };
 struct PlaceState {
   bool obj_dirty = true;  // hist_base / npages changed: the object groups are built and uploaded again
-  bool obj_huge = false;  // the object groups were built with NMG_PLACE_HUGE
+  bool obj_huge = false;  // the object groups were built with every member (NMG_PLACE_HUGE, or the cost source
+                          // on an engine with NMG_COST_SCOPE_ALL: place_all_members)
   PlaceDev obj;
   DevBuf<uint32_t> d_thr, d_noff, d_bcnt;
   DevBuf<uint64_t> d_pvcnt, d_boff, d_part;
@@ -597,6 +606,7 @@ int cells_prepare(nmg_engine* h);
 int cells_fill(nmg_engine* h, const RowSet<uint32_t, 4>& s, uint32_t* rows);  // rows_get's fill for the page cells
 int timeline_prepare(nmg_engine* h);
 int cost_prepare(nmg_engine* h);
+int cost_fill(nmg_engine* h, const RowSet<uint64_t, 4>& s, uint64_t* rows);  // rows_get's fill for the page cost cells
 // What a report has before its rows: the counters downloaded, and res zeroed
 // but for nb_threads, match_samples = 1 and what the call-site registry reads
 // per entry, in the report's walk order (nmg_walk_order.h; meta follows it).

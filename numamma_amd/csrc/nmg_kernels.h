@@ -177,6 +177,11 @@ struct Params {
   uint64_t* cost;
   uint32_t cost_bucket_mask, cost_access_mask, cost_metric;
   uint32_t cost_rounds;  // cost_add's merge rounds (kCostRounds)
+  // the sparse entries' cost cells (NMG_COST_SCOPE_ALL): one u64 per slot of
+  // the sparse page table, the cost of key k at the slot the count table gave
+  // k (sparse_slot); null unless that scope is set and the table exists.  Not
+  // tied to `cost`: a table without a dense cell has this array only.
+  uint64_t* sparse_cost;
 };
 
 // merge rounds of cost_add (nmg_device.h) before the remaining lanes add
@@ -236,6 +241,7 @@ struct ResetParams {
   uint32_t* bufcnt;
   uint64_t n_bufcnt;
   unsigned long long* found;  // zeroed
+  uint64_t* sparse_cost;      // cleared with the sparse table (a reused slot keeps no old cost); may be null
 };
 
 // Launchers (nmg_kernels.hip).  `mode` = kModeDenseObj | kModeDensePage.
@@ -249,6 +255,9 @@ hipError_t launch_merge(hipStream_t s, void* dst, const void* src, uint64_t n, i
 // packed page histogram (nmg_hist_pack / nmg_hist_unpack); ncells a multiple of 4
 // sparse_download: the used slots of the sparse table as (key, count) u64 pairs, *cnt of them
 hipError_t launch_sparse_compact(hipStream_t s, const uint64_t* keys, const uint32_t* vals, uint64_t cap,
+                                 uint64_t* out, unsigned long long* cnt);
+// the same over the sparse cost cells: (key, cost) pairs of the slots with a non-zero cost
+hipError_t launch_sparse_compact(hipStream_t s, const uint64_t* keys, const uint64_t* cost, uint64_t cap,
                                  uint64_t* out, unsigned long long* cnt);
 hipError_t launch_sparse_insert(hipStream_t s, uint64_t* keys, uint32_t* vals, uint64_t cap, const uint64_t* pairs,
                                 uint64_t n);
@@ -365,8 +374,13 @@ struct PlaceHugeParams {
   uint32_t* bcnt;           // PlaceParams::bcnt
   const uint64_t* boff;     // PlaceParams::boff
   uint64_t* rows;           // PlaceParams::rows
+  // NMG_PLACE_PAGE_COST on an engine with NMG_COST_SCOPE_ALL: the cost cells folded instead
+  // (sparse_cost parallel to sparse_vals, cost at the histogram's index; `cost` null: no dense cell)
+  const uint64_t* sparse_cost;
+  const uint64_t* cost;
 };
-hipError_t launch_place_huge_extract(hipStream_t s, const PlaceHugeParams& p, bool sparse);
+// from_cost: the items' values are the cost cells (the u64 instances)
+hipError_t launch_place_huge_extract(hipStream_t s, const PlaceHugeParams& p, bool sparse, bool from_cost = false);
 // the n items of keys / vals sorted by key into skeys / svals (tmp: tmp_bytes of workspace)
 size_t place_huge_sort_bytes(uint64_t n);
 hipError_t launch_place_huge_sort(hipStream_t s, const PlaceHugeParams& p, uint64_t n, void* tmp, size_t tmp_bytes);

@@ -340,6 +340,7 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
     atomicMin(fp, ord);
   }
   sub_stamp<TIMING>(st, 2);
+  uint32_t sslot = kNoSlot;  // (COST) a sparse entry's sample: the slot of its page cell
   if (p.flags & NMG_F_PAGE_HIST) {
     // ma_get_block: page_no = (int)((addr - buffer_addr) / 4096) (mem_analyzer.c:530-531)
     const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
@@ -355,8 +356,10 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
       }
     } else {
       const uint32_t sidx = p.entries[e].sidx;
-      if (sidx != ~0u)  // huge objects ([stack]): hashed cells in global memory
-        sparse_add(p, sparse_key(sidx, th, page), in1 ? b1.seq : b0.seq, off, 1u);
+      if (sidx != ~0u) {  // huge objects ([stack]): hashed cells in global memory
+        const uint32_t s = sparse_add(p, sparse_key(sidx, th, page), in1 ? b1.seq : b0.seq, off, 1u);
+        if (COST) sslot = s;
+      }
     }
   }
   sub_stamp<TIMING>(st, 3);
@@ -376,6 +379,10 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
     const uint64_t v = m.hist != kHistSparse ? cost_value(p, access, lvl, w) : 0ull;
     cost_add<false>(p, v != 0, uint64_t(th) * p.hist_cells + (m.hist + page), v, p.cost_rounds);
   }
+  // ... and of a sparse entry, with NMG_COST_SCOPE_ALL: the cell parallel to
+  // the page count's slot (not gated on p.cost: a table may have no dense
+  // cell).  The lane's own add: no cross-lane step in this diverged region.
+  if (COST && p.sparse_cost && sslot != kNoSlot) sparse_cost_add(p, sslot, cost_value(p, access, lvl, w));
 }
 
 // ---------------------------------------------------------------------------
@@ -981,6 +988,7 @@ __global__ __launch_bounds__(256) void reset_kernel(ResetParams r) {
   for (uint64_t i = i0; i < scap; i += stride) {
     r.sparse_keys[i] = ~0ull;
     r.sparse_vals[i] = 0;
+    if (r.sparse_cost) r.sparse_cost[i] = 0;  // (every cost add follows a sparse_add that set the flag)
   }
   for (uint64_t i = i0; i < r.n_bufcnt; i += stride) r.bufcnt[i] = 0;
   if (i0 == 0 && r.found) *r.found = 0;
@@ -1211,15 +1219,17 @@ __global__ __launch_bounds__(256) void hist_ovf_add_kernel(uint32_t* hist, uint6
 }
 
 // The sparse table's used slots as (key, count) pairs (order: any; the host
-// sorts), one counter add per wave that holds one.
-__global__ __launch_bounds__(256) void sparse_compact_kernel(const uint64_t* keys, const uint32_t* vals, uint64_t cap,
+// sorts), one counter add per wave that holds one.  VAL: u32 the page counts,
+// u64 the sparse cost cells (the slots with a non-zero cost).
+template <class VAL>
+__global__ __launch_bounds__(256) void sparse_compact_kernel(const uint64_t* keys, const VAL* vals, uint64_t cap,
                                                              uint64_t* out, unsigned long long* cnt) {
   const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
   const int lane = threadIdx.x & 63;
   for (uint64_t base = uint64_t(blockIdx.x) * blockDim.x; base < cap; base += stride) {
     const uint64_t i = base + threadIdx.x;
     const uint64_t key = i < cap ? keys[i] : ~0ull;
-    const uint32_t v = i < cap ? vals[i] : 0u;
+    const VAL v = i < cap ? vals[i] : VAL(0);
     const bool used = key != ~0ull && v != 0;
     const uint64_t m = __ballot(used);
     if (!m) continue;
@@ -1268,7 +1278,7 @@ hipError_t launch_attribute(bool timing, int mode, uint32_t grid, hipStream_t s,
   static const AttributeKernel k[2][2][8] = {{NMG_ATTR8(false, false), NMG_ATTR8(true, false)},
                                              {NMG_ATTR8(false, true), NMG_ATTR8(true, true)}};
 #undef NMG_ATTR8
-  hipLaunchKernelGGL(k[p.cost ? 1 : 0][timing ? 1 : 0][mode & 7], dim3(grid), dim3(kWG), 0, s, p);
+  hipLaunchKernelGGL(k[p.cost || p.sparse_cost ? 1 : 0][timing ? 1 : 0][mode & 7], dim3(grid), dim3(kWG), 0, s, p);
   return hipGetLastError();
 }
 
@@ -1604,7 +1614,15 @@ hipError_t launch_sparse_compact(hipStream_t s, const uint64_t* keys, const uint
                                  uint64_t* out, unsigned long long* cnt) {
   if (!cap) return hipSuccess;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((cap + 255) / 256, 2048);
-  hipLaunchKernelGGL(sparse_compact_kernel, dim3(grid), dim3(256), 0, s, keys, vals, cap, out, cnt);
+  hipLaunchKernelGGL(sparse_compact_kernel<uint32_t>, dim3(grid), dim3(256), 0, s, keys, vals, cap, out, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_compact(hipStream_t s, const uint64_t* keys, const uint64_t* cost, uint64_t cap,
+                                 uint64_t* out, unsigned long long* cnt) {
+  if (!cap) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((cap + 255) / 256, 2048);
+  hipLaunchKernelGGL(sparse_compact_kernel<uint64_t>, dim3(grid), dim3(256), 0, s, keys, cost, cap, out, cnt);
   return hipGetLastError();
 }
 

@@ -133,8 +133,11 @@ __global__ __launch_bounds__(256) void place_blocks_kernel(PlaceParams p) {
 // Extract: one lane per slot of the sparse table (SPARSE), or per (thread,
 // cell) of the huge groups' dense members.  A non-zero cell of a member, on a
 // page below the member's limit, is an item; the items of a wave are appended
-// with one atomic.  keys == null: the items are only counted.
-template <bool SPARSE>
+// with one atomic.  keys == null: the items are only counted.  COST: the
+// cells are the page cost cells (NMG_PLACE_PAGE_COST on an engine with
+// NMG_COST_SCOPE_ALL) -- a slot's sparse cost cell, a dense member's cost cell
+// at the histogram's index -- in instances of their own.
+template <bool SPARSE, bool COST>
 __global__ __launch_bounds__(256) void place_huge_extract_kernel(PlaceHugeParams p, uint64_t total) {
   const uint32_t lane = threadIdx.x & 63;
   for (uint64_t i0 = blockIdx.x * 256ull + (threadIdx.x & ~63u); i0 < total; i0 += gridDim.x * 256ull) {
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(256) void place_huge_extract_kernel(PlaceHugeParams
         const uint32_t sidx = sparse_key_idx(k), th = sparse_key_thread(k), page = sparse_key_page(k);
         if (k != kEmpty64 && sidx < p.nsent && th < p.T) {
           const uint32_t rank = p.s_rank[sidx];
-          val = p.sparse_vals[i];
+          val = COST ? p.sparse_cost[i] : (uint64_t)p.sparse_vals[i];
           has = rank != kEmpty32 && page < p.s_lim[sidx] && val != 0;
           key = (uint64_t(rank) << kPlaceRankShift) | (uint64_t(page) << kPlaceNodeBits) | p.tnode[th];
         }
@@ -166,7 +169,8 @@ __global__ __launch_bounds__(256) void place_huge_extract_kernel(PlaceHugeParams
           }
         }
         const uint64_t page = c - p.dm_off[d];
-        val = p.hist[uint64_t(th) * p.hist_cells + p.dm_base[d] + page];
+        const uint64_t cell = uint64_t(th) * p.hist_cells + p.dm_base[d] + page;
+        val = COST ? p.cost[cell] : (uint64_t)p.hist[cell];
         has = val != 0;
         key = (uint64_t(p.dm_rank[d]) << kPlaceRankShift) | (page << kPlaceNodeBits) | p.tnode[th];
       }
@@ -278,11 +282,15 @@ __global__ __launch_bounds__(256) void place_huge_emit_kernel(PlaceHugeParams p,
 
 static uint32_t huge_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 1u << 16); }
 
-hipError_t launch_place_huge_extract(hipStream_t s, const PlaceHugeParams& p, bool sparse) {
+hipError_t launch_place_huge_extract(hipStream_t s, const PlaceHugeParams& p, bool sparse, bool from_cost) {
   const uint64_t total = sparse ? p.sparse_cap : p.dcells * p.T;
   if (!total) return hipSuccess;
-  if (sparse) hipLaunchKernelGGL(place_huge_extract_kernel<true>, dim3(huge_grid(total)), dim3(256), 0, s, p, total);
-  else hipLaunchKernelGGL(place_huge_extract_kernel<false>, dim3(huge_grid(total)), dim3(256), 0, s, p, total);
+  if (from_cost && !(sparse ? p.sparse_cost != nullptr : p.cost != nullptr)) return hipErrorInvalidValue;
+  const dim3 grid(huge_grid(total));
+  if (sparse && from_cost) hipLaunchKernelGGL((place_huge_extract_kernel<true, true>), grid, dim3(256), 0, s, p, total);
+  else if (sparse) hipLaunchKernelGGL((place_huge_extract_kernel<true, false>), grid, dim3(256), 0, s, p, total);
+  else if (from_cost) hipLaunchKernelGGL((place_huge_extract_kernel<false, true>), grid, dim3(256), 0, s, p, total);
+  else hipLaunchKernelGGL((place_huge_extract_kernel<false, false>), grid, dim3(256), 0, s, p, total);
   return hipGetLastError();
 }
 size_t place_huge_sort_bytes(uint64_t n) {
@@ -429,21 +437,25 @@ int upload_groups(nmg_engine* h, PlaceDev& d, const PlaceGroups& g, const std::v
 // dense groups' count pass, on the same stream): *m list items left in q's
 // arrays for launch_place_huge_emit.
 int run_huge(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, const PlaceParams& p, PlaceHugeParams& q,
-             uint64_t* m) {
+             uint64_t* m, bool from_cost) {
   *m = 0;
   PlaceState& S = h->place;
   hipStream_t st = h->stream;
   bool sparse = false;  // nothing inserted since the last reset: the table is not read
   int rc = sparse_nonempty(h, &sparse);
   if (rc) return rc;
-  sparse = sparse && d.nsent && h->cnt.d_sparse_keys && h->cnt.d_sparse_vals;
-  if (!sparse && !d.DM) return NMG_OK;
+  sparse = sparse && d.nsent && h->cnt.d_sparse_keys && h->cnt.d_sparse_vals && (!from_cost || h->cost.d_sparse);
+  // (from the cost cells: the dense members' exist, or the table has no dense cell and they have none)
+  const bool dm = d.DM && (!from_cost || p.cost);
+  if (!sparse && !dm) return NMG_OK;
   HIP_TRY(h, alloc_copy(h, S.d_tnode, map.node));
   HIP_TRY(h, S.d_hn.reserve(1));
   HIP_TRY(h, S.d_hgfirst.reserve(d.H));
   q.sparse_keys = h->cnt.d_sparse_keys;
   q.sparse_vals = h->cnt.d_sparse_vals;
   q.sparse_cap = h->sparse_cap;
+  q.sparse_cost = from_cost ? h->cost.d_sparse.get() : nullptr;
+  q.cost = from_cost ? p.cost : nullptr;
   q.nsent = d.nsent;
   q.s_rank = d.s_rank;
   q.s_lim = d.s_lim;
@@ -468,8 +480,8 @@ int run_huge(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, const PlaceP
   uint64_t n = 0;
   for (int pass = 0; pass < 2; pass++) {
     HIP_TRY(h, hipMemsetAsync(S.d_hn, 0, 8, st));
-    if (sparse) HIP_TRY(h, launch_place_huge_extract(st, q, true));
-    if (d.DM) HIP_TRY(h, launch_place_huge_extract(st, q, false));
+    if (sparse) HIP_TRY(h, launch_place_huge_extract(st, q, true, from_cost));
+    if (dm) HIP_TRY(h, launch_place_huge_extract(st, q, false, from_cost));
     uint64_t got = 0;
     HIP_TRY(h, hipMemcpyAsync(&got, S.d_hn, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));  // (also: the thread map's vector was read)
@@ -555,7 +567,7 @@ int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, bool from_
   PlaceHugeParams q{};
   uint64_t m = 0;
   if (d.H) {
-    const int rc = run_huge(h, d, map, p, q, &m);
+    const int rc = run_huge(h, d, map, p, q, &m, from_cost);
     if (rc) return rc;
   }
   uint64_t nrows = 0;
@@ -574,10 +586,19 @@ int run_blocks(nmg_engine* h, const PlaceDev& d, const PlaceMap& map, bool from_
   return NMG_OK;
 }
 
+// every member entry contributes, the sparse ones included: NMG_PLACE_HUGE, or
+// the cost source on an engine whose cells were set with NMG_COST_SCOPE_ALL
+bool place_all_members(const nmg_engine* h, const nmg_placement_options* p) {
+  return (p->source & NMG_PLACE_HUGE) != 0 ||
+         (p->source == NMG_PLACE_PAGE_COST && h->cost.on && h->cost.scope == NMG_COST_SCOPE_ALL);
+}
+
 // what every placement call checks first
 int placement_begin(nmg_engine* h, const nmg_placement_options* p, PlaceMap& map) {
   if (p->source == (NMG_PLACE_PAGE_COST | NMG_PLACE_HUGE))
-    return fail(h, NMG_ERR_INVALID, "placement: NMG_PLACE_HUGE with NMG_PLACE_PAGE_COST: sparse entries have no cost cells");
+    return fail(h, NMG_ERR_INVALID, "placement: NMG_PLACE_HUGE with NMG_PLACE_PAGE_COST: sparse entries have no cost cells "
+                                    "unless the cells were set with them (set the cells with NMG_COST_SCOPE_ALL and use "
+                                    "NMG_PLACE_PAGE_COST)");
   if (placement_map(p, h->T, map)) return fail(h, NMG_ERR_INVALID, "placement options out of range");
   if ((h->flags & NMG_F_DEFAULT) != NMG_F_DEFAULT)
     return fail(h, NMG_ERR_INVALID, "placement needs NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST");
@@ -591,7 +612,7 @@ int placement_begin(nmg_engine* h, const nmg_placement_options* p, PlaceMap& map
 // the object blocks of the current results epoch and of p, left in place.rows
 int object_blocks_prepare(nmg_engine* h, const nmg_placement_options* p, const PlaceMap& map) {
   PlaceState& S = h->place;
-  const bool huge = (p->source & NMG_PLACE_HUGE) != 0;
+  const bool huge = place_all_members(h, p);
   if (S.obj_dirty || S.obj_huge != huge) {  // (the table's groups: uploaded once per table and flag)
     std::vector<uint64_t> npages, base;
     std::vector<uint8_t> dense;
@@ -661,7 +682,7 @@ extern "C" int nmg_report_placement(nmg_engine* h, const nmg_object_meta* meta, 
   std::vector<PlaceSite> sites;
   std::string err;
   rc = placement_site_groups(&in.res, meta, opts && opts->online, npages.data(), dense.data(), g, sites, err,
-                             (p->source & NMG_PLACE_HUGE) != 0);
+                             place_all_members(h, p));
   std::vector<uint64_t> rows;
   if (!rc) {
     PlaceDev d;

@@ -174,14 +174,16 @@ static void cell_layout_host(nmg_engine* h, std::vector<uint32_t>& np, std::vect
 
 // The sparse table's n compacted (key, count) words as rows (entry, thread,
 // page, count): each sparse entry's cells in (thread, page) order from row
-// soff[sparse idx] on.
+// soff[sparse idx] on.  W: u32 the page cells, u64 the page cost cells (the
+// words are then (key, cost)).
+template <class W>
 static void place_sparse_rows(const uint64_t* kv, uint64_t n, const std::vector<uint32_t>& sent_entry,
-                              const uint64_t* soff, uint32_t* rows) {
+                              const uint64_t* soff, W* rows) {
   const uint64_t nsent = sent_entry.size();
-  std::vector<std::vector<std::pair<uint64_t, uint32_t>>> per(nsent);
+  std::vector<std::vector<std::pair<uint64_t, W>>> per(nsent);
   for (uint64_t i = 0; i < n; i++) {
     const uint64_t k = kv[2 * i];
-    const uint32_t v = (uint32_t)kv[2 * i + 1];
+    const W v = (W)kv[2 * i + 1];
     const uint32_t s = sparse_key_idx(k);
     if (k == ~0ull || !v || s >= nsent || sent_entry[s] == ~0u) continue;
     per[s].push_back({(uint64_t(sparse_key_thread(k)) << 32) | sparse_key_page(k), v});
@@ -190,7 +192,7 @@ static void place_sparse_rows(const uint64_t* kv, uint64_t n, const std::vector<
     auto& l = per[s];
     if (l.empty()) continue;
     std::sort(l.begin(), l.end());
-    uint32_t* r = rows + soff[s] * 4;
+    W* r = rows + soff[s] * 4;
     for (const auto& c : l) {
       r[0] = sent_entry[s];
       r[1] = (uint32_t)(c.first >> 32);
@@ -238,13 +240,14 @@ static uint64_t* emit_rows(uint64_t* rows) { return rows; }
 
 // The dense rows of `cells` (the page histogram, or the cost cells at its
 // index; null: no dense cell) over cprep's layout and work arrays: counted per
-// entry, scanned into row offsets, emitted into s.d_rows.  with_sparse (page
-// cells only): the sparse table's entries are counted too, from the slots
-// sparse_download left in d_sparse_ck, and their first rows read back into
-// cprep.soff for cells_fill.  A pass ends before it returns, so the page
-// cells' and the cost cells' passes share the work arrays without meeting.
+// entry, scanned into row offsets, emitted into s.d_rows.  with_sparse: the
+// sparse table's entries are counted too, from the compacted words in
+// d_sparse_ck (sparse_download's (key, count), or cost_prepare's (key, cost)),
+// and their first rows read back into soff[nsent] for the fill (cells_fill /
+// cost_fill).  A pass ends before it returns, so the page cells' and the cost
+// cells' passes share the work arrays without meeting.
 template <class CELL, class RS>
-static int dense_rows(nmg_engine* h, const CELL* cells, RS& s, bool with_sparse, Lap lap) {
+static int dense_rows(nmg_engine* h, const CELL* cells, RS& s, bool with_sparse, uint64_t* soff, Lap lap) {
   const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   CellLayout& C = h->cprep.lay;
   uint64_t n = 0;
@@ -261,12 +264,12 @@ static int dense_rows(nmg_engine* h, const CELL* cells, RS& s, bool with_sparse,
     const int rc = scan_total(h, C.d_cnt, E, C.d_off, C.d_part, &n, [&]() -> hipError_t {
       if (!with_sparse) return hipSuccess;
       const hipError_t e = launch_gather_off(st, C.d_off, C.d_sent, (uint32_t)nsent, C.d_soff);
-      return e != hipSuccess ? e : hipMemcpyAsync(h->cprep.soff.data(), C.d_soff, nsent * 8, hipMemcpyDeviceToHost, st);
+      return e != hipSuccess ? e : hipMemcpyAsync(soff, C.d_soff, nsent * 8, hipMemcpyDeviceToHost, st);
     });
     if (rc) return rc;
     lap("count");
+    if (n) HIP_TRY(h, s.reserve(n));  // (sparse rows included: the fill copies s.n rows out)
     if (cells && n) {
-      HIP_TRY(h, s.reserve(n));
       HIP_TRY(h, launch_cells_emit(st, cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off,
                                    emit_rows(s.d_rows.get())));
       HIP_TRY(h, hipStreamSynchronize(st));
@@ -302,7 +305,7 @@ int cells_prepare(nmg_engine* h) {
   }
   lap("sparse");
   P.soff.assign(h->tab.sparse_entries.size(), 0);
-  rc = dense_rows(h, h->tab.cells() && h->E ? h->cnt.d_hist.get() : nullptr, P.rows, !k.empty(), lap);
+  rc = dense_rows(h, h->tab.cells() && h->E ? h->cnt.d_hist.get() : nullptr, P.rows, !k.empty(), P.soff.data(), lap);
   if (rc) return rc;
   if (lap.on) fprintf(stderr, "cells_prepare: %llu rows\n", (unsigned long long)P.rows.n);
   return NMG_OK;
@@ -343,7 +346,42 @@ int cost_prepare(nmg_engine* h) {
   rc = cprep_layout(h);
   if (rc) return rc;
   c.rows.n = 0;
-  return c.d_cells ? dense_rows(h, c.d_cells.get(), c.rows, false, Lap{false}) : NMG_OK;
+  // NMG_COST_SCOPE_ALL: the slots with a non-zero cost compacted on the device
+  // as (key, cost) words -- counted per entry by dense_rows, downloaded for
+  // cost_fill -- unless nothing was inserted since the last reset
+  c.sparse_kv.clear();
+  c.soff.assign(h->tab.sparse_entries.size(), 0);
+  bool any = false;
+  if (c.d_sparse && h->cnt.d_sparse_keys) {
+    rc = sparse_nonempty(h, &any);
+    if (rc) return rc;
+  }
+  if (any) {
+    HIP_TRY(h, h->cnt.d_sparse_ck.reserve(h->sparse_cap * 2 + 1));
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->cnt.d_sparse_ck + 2 * h->sparse_cap);
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 8, h->stream));
+    HIP_TRY(h, launch_sparse_compact(h->stream, h->cnt.d_sparse_keys, c.d_sparse.get(), h->sparse_cap,
+                                     h->cnt.d_sparse_ck, cnt));
+    uint64_t n = 0;
+    HIP_TRY(h, hipMemcpyAsync(&n, cnt, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    c.sparse_kv.resize(2 * n);
+    if (n) HIP_TRY(h, hipMemcpy(c.sparse_kv.data(), h->cnt.d_sparse_ck, 2 * n * 8, hipMemcpyDeviceToHost));
+    any = n != 0;
+  }
+  if (!c.d_cells && !any) return NMG_OK;
+  return dense_rows(h, c.d_cells.get(), c.rows, any, c.soff.data(), Lap{false});
+}
+
+// rows[s.n * 4]: the rows D2H (the dense ones; none where the table has no dense cell), the sparse rows placed
+int cost_fill(nmg_engine* h, const RowSet<uint64_t, 4>& s, uint64_t* rows) {
+  const PageCost& c = h->cost;
+  if (c.d_cells) {
+    const int rc = RowsCopy()(h, s, rows);
+    if (rc) return rc;
+  }
+  place_sparse_rows(c.sparse_kv.data(), c.sparse_kv.size() / 2, h->cprep.sent_entry, c.soff.data(), rows);
+  return NMG_OK;
 }
 
 extern "C" int64_t nmg_count_cost_cells(nmg_engine* h) {
@@ -353,7 +391,7 @@ extern "C" int64_t nmg_count_cost_cells(nmg_engine* h) {
 
 extern "C" int nmg_get_cost_cells(nmg_engine* h, uint64_t* rows, int64_t n) {
   if (!h || (n && !rows)) return NMG_ERR_INVALID;
-  return rows_get(h, h->cost.rows, cost_prepare, rows, n);
+  return rows_get(h, h->cost.rows, cost_prepare, rows, n, cost_fill);
 }
 
 // ---- access timeline rows: counted per segment, scanned and emitted on the
@@ -618,6 +656,8 @@ extern "C" int nmg_sparse_import(nmg_engine* h, const uint64_t* keys, const uint
   HIP_TRY(h, h->cnt.d_sparse_ck.reserve(h->sparse_cap * 2 + 1));
   HIP_TRY(h, hipMemsetAsync(h->cnt.d_sparse_keys, 0xff, h->sparse_cap * 8, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->cnt.d_sparse_vals, 0, h->sparse_cap * 4, h->stream));
+  // (the slots move: the sparse cost cells start again -- cost cells are not merged across ranks)
+  if (h->cost.d_sparse) HIP_TRY(h, hipMemsetAsync(h->cost.d_sparse, 0, h->sparse_cap * 8, h->stream));
   if (n) {
     std::vector<uint64_t> kv(2 * (size_t)n);
     for (int64_t i = 0; i < n; i++) {
@@ -791,7 +831,7 @@ extern "C" int nmg_results_end(nmg_engine* h, nmg_results_view* out) {
   if (nspc) {  // the sparse cells, each entry's in (thread, page) order at its rows
     std::vector<uint64_t> kv(2 * nspc);
     HIP_TRY(h, hipMemcpy(kv.data(), S.d_ck, 2 * nspc * 8, hipMemcpyDeviceToHost));
-    place_sparse_rows(kv.data(), nspc, S.sent_entry, S.h_soff, S.h_rows);
+    place_sparse_rows<uint32_t>(kv.data(), nspc, S.sent_entry, S.h_soff, S.h_rows);
   }
   memset(out, 0, sizeof(*out));
   global_counters(S.h_sum, S.h_min, S.h_max, out->global);

@@ -142,11 +142,15 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
   atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + e), (unsigned long long)((seq << 32) | off));
   if (!(p.flags & NMG_F_PAGE_HIST)) return;
   const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
+  uint32_t sslot = kNoSlot;  // (TL) a sparse entry's record: the slot of its page cell
   if (m.hist != kHistSparse) {
     atomicAdd(p.hist + uint64_t(th) * p.hist_cells + m.hist + page, 1u);
   } else {
     const uint32_t sidx = p.entries[e].sidx;
-    if (sidx != ~0u) sparse_add(p, sparse_key(sidx, th, page), seq, off, 1u);
+    if (sidx != ~0u) {
+      const uint32_t s = sparse_add(p, sparse_key(sidx, th, page), seq, off, 1u);
+      if (TL) sslot = s;
+    }
   }
   if (TL && p.tl) {  // access timeline: this lane's own add (the callers' lanes are diverged; no merge here)
     const uint64_t pad = p.entries[e].pad1;
@@ -156,6 +160,8 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
     const uint64_t v = cost_value(p, acc, lvl, w);
     cost_add<false>(p, v != 0, uint64_t(th) * p.hist_cells + m.hist + page, v, 0);
   }
+  // a sparse entry's cost cell (NMG_COST_SCOPE_ALL), parallel to its page count's slot; not gated on p.cost
+  if (TL && p.sparse_cost && sslot != kNoSlot) sparse_cost_add(p, sslot, cost_value(p, acc, lvl, w));
 }
 
 // ---------------------------------------------------------------------------
@@ -1033,7 +1039,8 @@ __global__ __launch_bounds__(256) void overflow_kernel(RouteParams rp) {
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     XRec xr = x_decode(rp.xl, rp.ovfx[i], rp.ovf16[i]);
     if (xr.esc) x_resolve(xr, rp.xl, rp.p.data, rp.p.sbufs);
-    const uint32_t lvl = ((rp.p.flags & NMG_F_OBJECT_LEVELS) || rp.p.cost)
+    // (cost_bucket_mask: non-zero exactly while page cost cells are set, dense or sparse)
+    const uint32_t lvl = ((rp.p.flags & NMG_F_OBJECT_LEVELS) || rp.p.cost_bucket_mask)
                              ? raw_mem_lvl(rp.p.data, rp.p.sbufs[xr.g(rp.xl)].offset + xr.off(rp.xl))
                              : 0u;
     direct_attribute<true>(rp.p, xr.addr, xr.ts, xr.w, xr.th, xr.acc, lvl, rp.seq0 + xr.g(rp.xl), xr.off(rp.xl),
@@ -1726,7 +1733,8 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
         // applies.
         const bool lev = (p.flags & NMG_F_OBJECT_LEVELS) != 0;
         const bool tlon = p.tl != nullptr;  // access timeline set: the matched records' cells
-        const bool cost = p.cost != nullptr;  // page cost cells set: the matched records' level and cell
+        // page cost cells set (dense or sparse: the mask is non-zero exactly then): the matched records' level and cell
+        const bool cost = p.cost_bucket_mask != 0;
         bool need[kLC], any = false;
 #pragma unroll
         for (int j = 0; j < kLC; j++) {
@@ -1803,15 +1811,25 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
           // re-read one).
           if (cost) {
             uint64_t hb[kLC];
-#pragma unroll
-            for (int j = 0; j < kLC; j++)
-              hb[j] = need[j] && erel[j] >= 0 ? p.entries[eid[j]].hist : kHistSparse;
+            uint32_t sx[kLC];  // (sparse entries: the sparse index, in the same 64 B)
 #pragma unroll
             for (int j = 0; j < kLC; j++) {
-              const uint64_t v = hb[j] != kHistSparse ? cost_value(p, xr[j].acc, lvl[j], w[j]) : 0ull;
+              const bool on = need[j] && erel[j] >= 0;
+              hb[j] = on ? p.entries[eid[j]].hist : kHistSparse;
+              sx[j] = on ? p.entries[eid[j]].sidx : kEmpty32;
+            }
+#pragma unroll
+            for (int j = 0; j < kLC; j++) {
+              const uint64_t cv = need[j] && erel[j] >= 0 ? cost_value(p, xr[j].acc, lvl[j], w[j]) : 0ull;
+              const uint64_t v = hb[j] != kHistSparse ? cv : 0ull;
               cost_add<true>(p, v != 0,
                              uint64_t(xr[j].th) * p.hist_cells + hb[j] + uint32_t(int(pofs[j] / kPageSize)), v,
                              p.cost_rounds);
+              // A sparse entry's cell (NMG_COST_SCOPE_ALL): outside the merge
+              // above (its DPP sums take the whole wave), the lane probes for
+              // the slot the page-cells block gave its key and adds singly.
+              if (p.sparse_cost && hb[j] == kHistSparse && sx[j] != kEmpty32 && cv)
+                sparse_cost_add(p, sparse_slot(p, sparse_key(sx[j], xr[j].th, uint32_t(int(pofs[j] / kPageSize)))), cv);
             }
           }
           vm_drain();
@@ -1997,7 +2015,8 @@ __global__ __launch_bounds__(kWG) void found_kernel(FoundParams r) {
 hipError_t launch_route(uint32_t grid, hipStream_t s, const RouteParams& r) {
   // (TL: an instance of its own for engines with a timeline or page cost cells
   // set, so that the other one is the code it was before either existed)
-  const bool timing = (r.p.flags & kDbgRouteTiming) != 0, tl = r.p.tl != nullptr || r.p.cost != nullptr;
+  const bool timing = (r.p.flags & kDbgRouteTiming) != 0, tl = r.p.tl != nullptr || r.p.cost != nullptr ||
+                                                                r.p.sparse_cost != nullptr;
   if (timing && tl) hipLaunchKernelGGL((route2_kernel<true, true>), dim3(grid), dim3(kR2WG), 0, s, r);
   else if (timing) hipLaunchKernelGGL((route2_kernel<true, false>), dim3(grid), dim3(kR2WG), 0, s, r);
   else if (tl) hipLaunchKernelGGL((route2_kernel<false, true>), dim3(grid), dim3(kR2WG), 0, s, r);
@@ -2039,7 +2058,7 @@ hipError_t launch_local(uint32_t grid, hipStream_t s, const LocalParams& r) {
                               kDbgLocalNoPage | kDbgLocalAtomics;
   const bool instr = (r.p.flags & kInstr) != 0, packed = r.pe_cmap != nullptr;
   const bool extra = (r.p.flags & NMG_F_OBJECT_LEVELS) != 0 || r.p.smatch != nullptr || r.p.tl != nullptr ||
-                     r.p.cost != nullptr;
+                     r.p.cost != nullptr || r.p.sparse_cost != nullptr;
   if (packed) {
     if (instr) launch_local_as<true, true>(extra, grid, s, r);
     else launch_local_as<false, true>(extra, grid, s, r);

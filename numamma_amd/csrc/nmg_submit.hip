@@ -654,6 +654,7 @@ Params base_params(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, co
     p.cost_access_mask = h->cost.opt.access_mask;
     p.cost_metric = h->cost.opt.metric;
     p.cost_rounds = h->cost.rounds;
+    p.sparse_cost = h->cnt.d_sparse_keys ? h->cost.d_sparse.get() : nullptr;  // (NMG_COST_SCOPE_ALL, else null)
   }
   return p;
 }

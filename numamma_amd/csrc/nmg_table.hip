@@ -557,8 +557,17 @@ extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
 // index, zeroed.  Nothing in the table changes: the kernels find a cell from
 // the entry's histogram base, which they have.
 extern "C" int nmg_set_page_cost(nmg_engine* h, const nmg_page_cost_options* o) {
+  return nmg_set_page_cost_ex(h, o, NMG_COST_SCOPE_DENSE);
+}
+
+// scope NMG_COST_SCOPE_ALL: also one u64 per slot of the sparse page table
+// (PageCost::d_sparse), within the same budget, whenever that table exists.
+extern "C" int nmg_set_page_cost_ex(nmg_engine* h, const nmg_page_cost_options* o, uint32_t scope) {
   if (!h) return NMG_ERR_INVALID;
   h->epoch++;
+  h->place.obj_dirty = true;  // (the object groups' members depend on the scope)
+  if (scope > NMG_COST_SCOPE_ALL)
+    return fail(h, NMG_ERR_INVALID, "nmg_set_page_cost_ex: scope is NMG_COST_SCOPE_DENSE or NMG_COST_SCOPE_ALL");
   if (h->multi || !h->workers.empty()) return fail(h, NMG_ERR_INVALID, "nmg_set_page_cost: not on a multi-GPU handle");
   constexpr uint32_t kNeed = NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST;
   if ((h->flags & kNeed) != kNeed)
@@ -581,18 +590,24 @@ extern "C" int nmg_set_page_cost(nmg_engine* h, const nmg_page_cost_options* o) 
   c.opt = *o;
   c.budget = o->budget_bytes ? o->budget_bytes : (1ull << 30);
   if (const char* r = getenv("NMG_COST_ROUNDS")) c.rounds = (uint32_t)std::min(64, std::max(0, atoi(r)));  // (see kCostRounds)
+  c.scope = scope;
   const uint64_t ncells = h->tab.cells() * h->T;  // (within the histogram's budget: no overflow)
-  if (ncells * 8 > c.budget) {
+  const uint64_t nsparse = scope == NMG_COST_SCOPE_ALL && h->cnt.d_sparse_keys ? h->sparse_cap : 0;  // (<= 2^31)
+  if ((ncells + nsparse) * 8 > c.budget) {
     char msg[160];
     snprintf(msg, sizeof(msg), "nmg_set_page_cost: the cells need %llu bytes (budget %llu)",
-             (unsigned long long)(ncells * 8), (unsigned long long)c.budget);
+             (unsigned long long)((ncells + nsparse) * 8), (unsigned long long)c.budget);
     return fail(h, NMG_ERR_CAPACITY, msg);
   }
   if (ncells) {
     HIP_TRY(h, c.d_cells.alloc(ncells));
     HIP_TRY(h, hipMemsetAsync(c.d_cells, 0, ncells * 8, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
+  if (nsparse) {
+    HIP_TRY(h, c.d_sparse.alloc(nsparse));
+    HIP_TRY(h, hipMemsetAsync(c.d_sparse, 0, nsparse * 8, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   c.on = true;
   h->cost = std::move(c);
   return NMG_OK;
@@ -650,19 +665,22 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
   const uint64_t cells = tab.cur.cells = tab.cur.padded_cells();
   // the page cost cells follow the histogram's layout, within their own budget
   const bool with_cost = h->cost.on;
-  if (with_cost && cells * T * 8 > h->cost.budget) {
+  const bool new_sparse = cur0.nsparse == 0 && tab.cur.nsparse && !h->cnt.d_sparse_keys;
+  // (NMG_COST_SCOPE_ALL: plus the sparse table's, the one this update brings included)
+  const bool cost_sparse = with_cost && h->cost.scope == NMG_COST_SCOPE_ALL && (h->cnt.d_sparse_keys || new_sparse);
+  const uint64_t cost_bytes = (cells * T + (cost_sparse ? h->sparse_cap : 0)) * 8;
+  if (with_cost && cost_bytes > h->cost.budget) {
     char msg[160];
     snprintf(msg, sizeof(msg), "nmg_update_objects: the page cost cells need %llu bytes (budget %llu)",
-             (unsigned long long)(cells * T * 8), (unsigned long long)h->cost.budget);
+             (unsigned long long)cost_bytes, (unsigned long long)h->cost.budget);
     return fail_rb(NMG_ERR_CAPACITY, msg);
   }
   // id-indexed counters, re-laid out for newE entries
   const uint64_t n_sum = sum64_words(newE, levels), n_min = min64_words(newE);
-  DevBuf<uint64_t> sum, mn, skeys, cost;
+  DevBuf<uint64_t> sum, mn, skeys, cost, scost;
   DevBuf<uint32_t> hist, svals, sdirty;
   DevBuf<unsigned long long> pk;
   DevBuf<DevEntry> ent;
-  const bool new_sparse = cur0.nsparse == 0 && tab.cur.nsparse && !h->cnt.d_sparse_keys;
   // (the new arrays are released on return, after the copies into them have drained)
   auto undo = [&](hipError_t e, const char* what) {
     (void)hipStreamSynchronize(h->stream);
@@ -683,6 +701,9 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
         (e = hipMemsetAsync(svals, 0, h->sparse_cap * 4, st)) != hipSuccess ||
         (e = hipMemsetAsync(sdirty, 0, 2 * 4, st)) != hipSuccess)
       return undo(e, "sparse page table");
+    if (cost_sparse && ((e = scost.alloc(h->sparse_cap)) != hipSuccess ||
+                        (e = hipMemsetAsync(scost, 0, h->sparse_cap * 8, st)) != hipSuccess))
+      return undo(e, "sparse page cost cells");
   }
   // the global words as they are, the count/weight rows with the new stride,
   // the level rows and ordinals behind them, the error word at its new place
@@ -743,6 +764,7 @@ int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_ob
     h->cnt.d_sparse_keys = std::move(skeys);
     h->cnt.d_sparse_vals = std::move(svals);
     h->cnt.d_sparse_dirty = std::move(sdirty);
+    if (scost) h->cost.d_sparse = std::move(scost);
   }
   return NMG_OK;
 }

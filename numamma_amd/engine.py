@@ -360,16 +360,21 @@ class Engine:
 
     # ---- page cost cells
     def set_page_cost(self, bucket_mask: Optional[int] = _lib.NMG_COST_MEMORY, access_mask: int = 3,
-                      metric: int = _lib.NMG_COST_WEIGHT, budget_bytes: int = 0, reserved: int = 0):
+                      metric: int = _lib.NMG_COST_WEIGHT, budget_bytes: int = 0, reserved: int = 0,
+                      scope: int = _lib.NMG_COST_SCOPE_DENSE):
         """nmg_set_page_cost: one u64 cell per (object, thread, page) summing,
         over the matched samples whose memory level falls in bucket_mask and
         whose access in access_mask, 1 or the sample's weight; counted by
-        every analysis from now on.  set_page_cost(None) drops the cells."""
-        if bucket_mask is None:
-            self._c(lib.nmg_set_page_cost(self.h, None))
-            return
-        o = _lib.nmg_page_cost_options(bucket_mask, access_mask, metric, reserved, budget_bytes)
-        self._c(lib.nmg_set_page_cost(self.h, C.byref(o)))
+        every analysis from now on.  set_page_cost(None) drops the cells.
+        scope = NMG_COST_SCOPE_ALL (nmg_set_page_cost_ex): the objects with
+        sparse page cells ([stack], arrays past the dense cap or the histogram
+        budget) get cost cells too."""
+        o = None if bucket_mask is None else C.byref(
+            _lib.nmg_page_cost_options(bucket_mask, access_mask, metric, reserved, budget_bytes))
+        if scope != _lib.NMG_COST_SCOPE_DENSE:
+            self._c(lib.nmg_set_page_cost_ex(self.h, o, scope))
+        else:
+            self._c(lib.nmg_set_page_cost(self.h, o))
 
     def cost_cells(self) -> np.ndarray:
         """The non-zero cost cells as u64 (entry, thread, page, value) rows,

@@ -16,6 +16,10 @@ one box by construction:
               selected record)
   allc_r<N>   (every bucket | NMG_COST_NA, both accesses, NMG_COST_COUNT): every
               record with a non-zero level adds
+--scopes 0,1 times each of them with nmg_set_page_cost (scope 0,
+NMG_COST_SCOPE_DENSE) and with nmg_set_page_cost_ex(NMG_COST_SCOPE_ALL) (scope
+1: the sparse entries, [stack] among them, get cost cells too; the variant's
+name then ends in _all).
 A checksum of the rows must be equal across the round settings of a variant
 (the tool fails otherwise).  Then one line in placement_timing.py's style:
 nmg_get_object_blocks from the cost cells against from the counts, median of
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", default="0,1,4,64", help="merge-round bounds to time")
+    ap.add_argument("--scopes", default="0", help="cost scopes to time: 0 dense, 1 all (comma-separated)")
     ap.add_argument("--nodes", type=int, default=8)
     ap.add_argument("--threshold", type=int, default=8)
     ap.add_argument("--runs", type=int, default=5)
@@ -92,13 +97,16 @@ def main():
              "allc": dict(bucket_mask=((1 << 18) - 1) | _lib.NMG_COST_NA, access_mask=3, metric=_lib.NMG_COST_COUNT)}
     out["costs"] = costs
     mul = np.array([3, 5, 7, 11], dtype="uint64")
-    for name, opt in costs.items():
+    for name, opt, scope in [(n + ("_all" if int(sc) else ""), o, int(sc)) for sc in args.scopes.split(",")
+                             for n, o in costs.items()]:
         sums = set()
         for r in [int(x) for x in args.rounds.split(",")]:
             os.environ["NMG_COST_ROUNDS"] = str(r)  # (read when the cells are set)
             eng = engine(_lib.NMG_F_DEFAULT)
-            eng.set_page_cost(**opt)
+            eng.set_page_cost(**opt, scope=scope)
             res = timed(eng)
+            if scope:
+                res["sparse_cells"] = int(eng.sparse_export()[0].shape[0])
             rows = eng.cost_cells()
             res.update(rows=int(rows.shape[0]), value_sum=int(rows[:, 3].sum(dtype="uint64")),
                        max_cell=int(rows[:, 3].max()) if rows.shape[0] else 0,
