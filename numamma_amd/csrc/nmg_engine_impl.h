@@ -223,6 +223,27 @@ struct EntryTable {
   }
 };
 
+// The sparse table's used slots compacted on the device: n interleaved (key,
+// value) u64 words (nmg_internal.h) in a block of 2 * cap + 1, n itself in the
+// last one.  Only reserve / words / count know that layout.
+struct SparseWords {
+  DevBuf<uint64_t> d;
+  uint64_t cap = 0;  // the table's slots
+  hipError_t reserve(uint64_t slots) { return d.reserve(2 * (cap = slots) + 1); }
+  uint64_t* words() const { return d; }
+  unsigned long long* count() const { return reinterpret_cast<unsigned long long*>(d + 2 * cap); }
+  // enqueued: the slots of (keys, vals)[cap] with a key and a non-zero value
+  // (u32 counts, or u64 costs) into words(), their number into count()
+  template <class V>
+  hipError_t compact(hipStream_t st, const uint64_t* keys, const V* vals) const {
+    const hipError_t e = hipMemsetAsync(count(), 0, 8, st);
+    return e != hipSuccess ? e : launch_sparse_compact(st, keys, vals, cap, words(), count());
+  }
+  // the words on the host: count() read behind the engine stream's work (the
+  // one wait; not where the caller has it in *known), then the 2n words copied
+  int download(nmg_engine* h, std::vector<uint64_t>& kv, const uint64_t* known = nullptr) const;
+};
+
 // the counter arrays of one table (nmg_set_objects releases them with it),
 // n_* their word counts (nmg_internal.h's layout for the table's entries)
 struct Counters {
@@ -237,7 +258,7 @@ struct Counters {
   DevBuf<uint64_t> d_sparse_keys;
   DevBuf<uint32_t> d_sparse_vals;
   DevBuf<uint64_t> d_objcw;         // [entries][4] per-object counters laid out for the D2H
-  DevBuf<uint64_t> d_sparse_ck;     // [sparse_cap + 1] compacted (key, count) words + the count (sparse_download)
+  SparseWords d_sparse_ck;          // the synchronous getters' compaction: (key, count) or (key, cost) words
   DevBuf<uint32_t> d_sparse_dirty;  // [2] parity flags (see reset_kernel)
   DevBuf<unsigned long long> d_pk64;  // hashed object mode: packed long-tail counters (0 between launches)
   DevBuf<uint4> d_tlog;             // hashed object mode: long-tail log (see Params::tlog)
@@ -378,7 +399,7 @@ struct nmg_engine {
     CellLayout lay;
     DevBuf<uint64_t> d_sum, d_min, d_max, d_objcw, d_found;
     DevBuf<uint32_t> d_bufcnt;
-    DevBuf<uint64_t> d_ck;  // the sparse table's used slots, compacted (+ their count)
+    SparseWords d_ck;  // the sparse table's (key, count) words at nmg_results_begin
     DevBuf<uint4> d_rows;
     // pinned host copies
     PinBuf<uint64_t> h_sum, h_min, h_max, h_objcw, h_small, h_soff;  // h_small: [0] matched total, [1] rows,
@@ -627,7 +648,8 @@ int scan_total(nmg_engine* h, const uint32_t* cnt, uint64_t n, uint64_t* off, ui
 void* array_ptr(nmg_engine* h, int which, size_t* bytes);
 int scratch_u64(nmg_engine* h);
 int sparse_nonempty(nmg_engine* h, bool* out);
-int sparse_download(nmg_engine* h, std::vector<uint64_t>& k, std::vector<uint32_t>& v);
+int sparse_download(nmg_engine* h, std::vector<uint64_t>& kv);  // the (key, count) words, in the device's order
+int sparse_import_words(nmg_engine* h, const uint64_t* kv, uint64_t n);  // nmg_sparse_import over n such words
 int multi_create(nmg_engine* h, const nmg_options* opt);
 void multi_destroy(nmg_engine* h);
 int multi_analyze(nmg_engine* h);

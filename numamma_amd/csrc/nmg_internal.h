@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "numamma_gpu.h"
@@ -138,6 +139,58 @@ constexpr uint64_t sparse_key(uint32_t sidx, uint32_t th, uint32_t page) {
 constexpr uint32_t sparse_key_idx(uint64_t k) { return uint32_t(k >> 42); }
 constexpr uint32_t sparse_key_thread(uint64_t k) { return uint32_t((k >> 32) & 0x3ff); }
 constexpr uint32_t sparse_key_page(uint64_t k) { return uint32_t(k); }
+
+// The sparse table's cells on the host: interleaved u64 words, kv[2i] a key and
+// kv[2i + 1] its value (a u32 count, or a u64 cost) -- as the device compacts
+// them (SparseWords, nmg_engine_impl.h).  Plain C++: the engine and
+// tests/c/nmg_sparse_words_host.cpp use what follows.
+// By key; merge: each key once, the counts of equal keys summed in u32 as the table's cells are.
+inline void sparse_words_sort(std::vector<uint64_t>& kv, bool merge = false) {
+  std::vector<std::pair<uint64_t, uint64_t>> p(kv.size() / 2);
+  for (size_t i = 0; i < p.size(); i++) p[i] = {kv[2 * i], kv[2 * i + 1]};
+  std::sort(p.begin(), p.end());
+  size_t m = 0;
+  for (const auto& w : p) {
+    if (merge && m && kv[m - 2] == w.first) {
+      kv[m - 1] = uint32_t(kv[m - 1] + w.second);
+      continue;
+    }
+    kv[m++] = w.first;
+    kv[m++] = w.second;
+  }
+  kv.resize(m);
+}
+
+// The n words as rows (entry, thread, page, value): each sparse entry's cells
+// in (thread, page) order from row soff[sparse idx] on.  sent_entry: sparse idx
+// -> entry, ~0 for one that is no longer sparse.  W: u32 the page cells, u64
+// the page cost cells.
+template <class W>
+void place_sparse_rows(const uint64_t* kv, uint64_t n, const std::vector<uint32_t>& sent_entry, const uint64_t* soff,
+                       W* rows) {
+  const uint64_t nsent = sent_entry.size();
+  std::vector<std::vector<std::pair<uint64_t, W>>> per(nsent);
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t k = kv[2 * i];
+    const W v = (W)kv[2 * i + 1];
+    const uint32_t s = sparse_key_idx(k);
+    if (k == ~0ull || !v || s >= nsent || sent_entry[s] == ~0u) continue;
+    per[s].push_back({(uint64_t(sparse_key_thread(k)) << 32) | sparse_key_page(k), v});
+  }
+  for (uint64_t s = 0; s < nsent; s++) {
+    auto& l = per[s];
+    if (l.empty()) continue;
+    std::sort(l.begin(), l.end());
+    W* r = rows + soff[s] * 4;
+    for (const auto& c : l) {
+      r[0] = sent_entry[s];
+      r[1] = (uint32_t)(c.first >> 32);
+      r[2] = (uint32_t)c.first;
+      r[3] = c.second;
+      r += 4;
+    }
+  }
+}
 
 // ---- dump modes: what the report writer needs besides the counters
 struct DumpBuffer {

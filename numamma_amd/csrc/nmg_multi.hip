@@ -244,10 +244,7 @@ int multi_finish(nmg_engine* h) {
   // cumulative: the per-buffer matched counts are gathered only when asked
   // (engine_download), the report needs their total
   std::vector<uint32_t> ns;
-  std::vector<uint64_t> keys;
-  std::vector<uint32_t> vals;
-  std::vector<uint64_t> k0;
-  std::vector<uint32_t> v0;
+  std::vector<uint64_t> kv, part;  // the workers' (key, count) words
   uint64_t found = 0;
   int rc = NMG_OK;
   for (nmg_engine* w : h->workers) {
@@ -261,26 +258,14 @@ int multi_finish(nmg_engine* h) {
     uint64_t f = 0;
     if (w->d_found) HIP_TRY(h, hipMemcpy(&f, w->d_found, 8, hipMemcpyDeviceToHost));
     found += f;
-    rc = sparse_download(w, k0, v0);
+    rc = sparse_download(w, part);
     if (rc) return fail(h, rc, w->last_error);
-    keys.insert(keys.end(), k0.begin(), k0.end());
-    vals.insert(vals.end(), v0.begin(), v0.end());
+    kv.insert(kv.end(), part.begin(), part.end());
   }
   HIP_TRY(h, hipSetDevice(h->device));
   if (h->cnt.d_sparse_keys) {
-    std::vector<size_t> ord(keys.size());
-    for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-    std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return keys[a] < keys[b]; });
-    std::vector<uint64_t> mk;
-    std::vector<uint32_t> mv;
-    for (size_t i : ord) {
-      if (!mk.empty() && mk.back() == keys[i]) mv.back() += vals[i];
-      else {
-        mk.push_back(keys[i]);
-        mv.push_back(vals[i]);
-      }
-    }
-    rc = nmg_sparse_import(h, mk.data(), mv.data(), (int64_t)mk.size());
+    sparse_words_sort(kv, true);
+    rc = sparse_import_words(h, kv.data(), kv.size() / 2);
     if (rc) return rc;
   }
   std::vector<uint32_t> nf(ns.size(), 0);

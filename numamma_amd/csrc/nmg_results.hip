@@ -158,70 +158,64 @@ int CellLayout::ensure(nmg_engine* h, uint64_t newE, uint64_t new_nsent) {
   return NMG_OK;
 }
 
-// the layout's host side: dense pages per entry (0: sparse), and the sparse
-// entries as the current table has them (sparse idx -> entry, ~0: no longer
-// sparse -- an online update gave it dense cells)
-static void cell_layout_host(nmg_engine* h, std::vector<uint32_t>& np, std::vector<uint32_t>& sent_entry) {
+// The table's cell layout into L, once per table: the entries' first cells,
+// their dense pages (0: sparse) and the sparse entries as the current table
+// has them (sparse idx -> entry; in sent_entry ~0 for one that is no longer
+// sparse -- an online update gave it dense cells).  copy(h, dst, src, bytes) is
+// the caller's H2D copy.
+template <class Copy>
+static int layout_upload(nmg_engine* h, CellLayout& L, std::vector<uint32_t>& sent_entry, Copy copy) {
+  if (!L.meta_dirty) return NMG_OK;
   const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
-  np.resize(E);
+  std::vector<uint32_t> np(E);
   for (uint64_t e = 0; e < E; e++) np[e] = h->tab.hist_base[e] == kHistSparse ? 0u : (uint32_t)h->tab.npages[e];
   sent_entry.resize(nsent);
   for (uint64_t s = 0; s < nsent; s++) {
     const uint32_t e = h->tab.sparse_entries[s];
     sent_entry[s] = h->tab.hist_base[e] == kHistSparse ? e : ~0u;
   }
+  int rc = copy(h, L.d_base.get(), h->tab.hist_base.data(), E * 8);
+  if (!rc) rc = copy(h, L.d_np.get(), np.data(), E * 4);
+  if (!rc) rc = copy(h, L.d_sent.get(), h->tab.sparse_entries.data(), nsent * 4);
+  if (!rc) L.meta_dirty = false;
+  return rc;
 }
 
-// The sparse table's n compacted (key, count) words as rows (entry, thread,
-// page, count): each sparse entry's cells in (thread, page) order from row
-// soff[sparse idx] on.  W: u32 the page cells, u64 the page cost cells (the
-// words are then (key, cost)).
-template <class W>
-static void place_sparse_rows(const uint64_t* kv, uint64_t n, const std::vector<uint32_t>& sent_entry,
-                              const uint64_t* soff, W* rows) {
-  const uint64_t nsent = sent_entry.size();
-  std::vector<std::vector<std::pair<uint64_t, W>>> per(nsent);
-  for (uint64_t i = 0; i < n; i++) {
-    const uint64_t k = kv[2 * i];
-    const W v = (W)kv[2 * i + 1];
-    const uint32_t s = sparse_key_idx(k);
-    if (k == ~0ull || !v || s >= nsent || sent_entry[s] == ~0u) continue;
-    per[s].push_back({(uint64_t(sparse_key_thread(k)) << 32) | sparse_key_page(k), v});
-  }
-  for (uint64_t s = 0; s < nsent; s++) {
-    auto& l = per[s];
-    if (l.empty()) continue;
-    std::sort(l.begin(), l.end());
-    W* r = rows + soff[s] * 4;
-    for (const auto& c : l) {
-      r[0] = sent_entry[s];
-      r[1] = (uint32_t)(c.first >> 32);
-      r[2] = (uint32_t)c.first;
-      r[3] = c.second;
-      r += 4;
-    }
-  }
+// One page-cell row pass over a layout, each step enqueued on the engine
+// stream: the synchronous getters (dense_rows) and nmg_results_begin run these.
+// pass_count: per entry the rows of `cells` (the page histogram, or the cost
+// cells at its index; null: no dense cell), then those of the sparse entries in
+// the compacted words sw (null: none), into L.d_cnt; its scan gives L.d_off.
+template <class CELL>
+static hipError_t pass_count(nmg_engine* h, CellLayout& L, const CELL* cells, const SparseWords* sw) {
+  hipError_t e = cells ? launch_cells_count(h->stream, cells, h->tab.cells(), h->T, L.d_base, L.d_np, h->E, L.d_cnt)
+                       : hipMemsetAsync(L.d_cnt, 0, h->E * 4, h->stream);
+  if (e == hipSuccess && sw)
+    e = launch_cells_sparse_count(h->stream, sw->words(), sw->count(), sw->cap, L.d_sent,
+                                  (uint32_t)h->tab.sparse_entries.size(), L.d_base, L.d_cnt);
+  return e;
+}
+// the dense rows at their offsets (launch_cells_emit writes a page-cell row as one uint4)
+static uint4* emit_rows(uint32_t* rows) { return reinterpret_cast<uint4*>(rows); }
+template <class ROW>
+static ROW* emit_rows(ROW* rows) { return rows; }
+template <class CELL, class ROW>
+static hipError_t pass_emit(nmg_engine* h, CellLayout& L, const CELL* cells, ROW* rows) {
+  return launch_cells_emit(h->stream, cells, h->tab.cells(), h->T, L.d_base, L.d_np, h->E, L.d_off, emit_rows(rows));
+}
+// the sparse entries' first rows into L.d_soff
+static hipError_t pass_soff(nmg_engine* h, CellLayout& L) {
+  return launch_gather_off(h->stream, L.d_off, L.d_sent, (uint32_t)h->tab.sparse_entries.size(), L.d_soff);
 }
 
-// the table's cell layout in cprep.lay, uploaded once per table (the page
-// cells' and the page cost cells' row passes)
+// cprep.lay for the current table (the page cells' and the page cost cells' row passes)
 static int cprep_layout(nmg_engine* h) {
-  const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   auto& P = h->cprep;
-  CellLayout& C = P.lay;
-  int rc = C.ensure(h, E, nsent);
-  if (rc) return rc;
-  if (C.meta_dirty) {
-    std::vector<uint32_t> np;
-    cell_layout_host(h, np, P.sent_entry);
-    if (E) {
-      HIP_TRY(h, hipMemcpy(C.d_base, h->tab.hist_base.data(), E * 8, hipMemcpyHostToDevice));
-      HIP_TRY(h, hipMemcpy(C.d_np, np.data(), E * 4, hipMemcpyHostToDevice));
-    }
-    if (nsent) HIP_TRY(h, hipMemcpy(C.d_sent, h->tab.sparse_entries.data(), nsent * 4, hipMemcpyHostToDevice));
-    C.meta_dirty = false;
-  }
-  return NMG_OK;
+  const int rc = P.lay.ensure(h, h->E, h->tab.sparse_entries.size());
+  return rc ? rc : layout_upload(h, P.lay, P.sent_entry, [](nmg_engine* h, void* dst, const void* src, size_t n) -> int {
+    if (n) HIP_TRY(h, hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
+    return NMG_OK;
+  });
 }
 
 struct Lap {  // NMG_CELLS_TIMING: the page cells' phase times on stderr
@@ -234,50 +228,64 @@ struct Lap {  // NMG_CELLS_TIMING: the page cells' phase times on stderr
   }
 };
 
-// (launch_cells_emit writes a page-cell row as one uint4)
-static uint4* emit_rows(uint32_t* rows) { return reinterpret_cast<uint4*>(rows); }
-static uint64_t* emit_rows(uint64_t* rows) { return rows; }
-
-// The dense rows of `cells` (the page histogram, or the cost cells at its
-// index; null: no dense cell) over cprep's layout and work arrays: counted per
-// entry, scanned into row offsets, emitted into s.d_rows.  with_sparse: the
-// sparse table's entries are counted too, from the compacted words in
-// d_sparse_ck (sparse_download's (key, count), or cost_prepare's (key, cost)),
-// and their first rows read back into soff[nsent] for the fill (cells_fill /
+// The rows of one synchronous prepare over cprep's layout and work arrays:
+// counted per entry -- the dense cells of `cells`, and the sparse table's from
+// the words sw that the caller has just compacted and downloaded (null: none)
+// -- scanned into row offsets, the dense ones emitted into s.d_rows; the sparse
+// entries' first rows are read back into soff[nsent] for the fill (cells_fill /
 // cost_fill).  A pass ends before it returns, so the page cells' and the cost
 // cells' passes share the work arrays without meeting.
 template <class CELL, class RS>
-static int dense_rows(nmg_engine* h, const CELL* cells, RS& s, bool with_sparse, uint64_t* soff, Lap lap) {
+static int dense_rows(nmg_engine* h, const CELL* cells, RS& s, const SparseWords* sw, uint64_t* soff, Lap lap) {
   const uint64_t E = h->E, nsent = h->tab.sparse_entries.size();
   CellLayout& C = h->cprep.lay;
   uint64_t n = 0;
   if (E) {
-    hipStream_t st = h->stream;
-    if (cells)
-      HIP_TRY(h, launch_cells_count(st, cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_cnt));
-    else
-      HIP_TRY(h, hipMemsetAsync(C.d_cnt, 0, E * 4, st));
-    if (with_sparse)
-      HIP_TRY(h, launch_cells_sparse_count(st, h->cnt.d_sparse_ck,
-                                           reinterpret_cast<const unsigned long long*>(h->cnt.d_sparse_ck + 2 * h->sparse_cap),
-                                           h->sparse_cap, C.d_sent, (uint32_t)nsent, C.d_base, C.d_cnt));
+    HIP_TRY(h, pass_count(h, C, cells, sw));
     const int rc = scan_total(h, C.d_cnt, E, C.d_off, C.d_part, &n, [&]() -> hipError_t {
-      if (!with_sparse) return hipSuccess;
-      const hipError_t e = launch_gather_off(st, C.d_off, C.d_sent, (uint32_t)nsent, C.d_soff);
-      return e != hipSuccess ? e : hipMemcpyAsync(soff, C.d_soff, nsent * 8, hipMemcpyDeviceToHost, st);
+      if (!sw) return hipSuccess;
+      const hipError_t e = pass_soff(h, C);
+      return e != hipSuccess ? e : hipMemcpyAsync(soff, C.d_soff, nsent * 8, hipMemcpyDeviceToHost, h->stream);
     });
     if (rc) return rc;
     lap("count");
     if (n) HIP_TRY(h, s.reserve(n));  // (sparse rows included: the fill copies s.n rows out)
     if (cells && n) {
-      HIP_TRY(h, launch_cells_emit(st, cells, h->tab.cells(), h->T, C.d_base, C.d_np, (uint32_t)E, C.d_off,
-                                   emit_rows(s.d_rows.get())));
-      HIP_TRY(h, hipStreamSynchronize(st));
+      HIP_TRY(h, pass_emit(h, C, cells, s.d_rows.get()));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     lap("emit");
   }
   s.n = (int64_t)n;
   return NMG_OK;
+}
+
+int SparseWords::download(nmg_engine* h, std::vector<uint64_t>& kv, const uint64_t* known) const {
+  uint64_t n = known ? *known : 0;
+  if (!known) {
+    HIP_TRY(h, hipMemcpyAsync(&n, count(), 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  kv.resize(2 * n);
+  if (n) HIP_TRY(h, hipMemcpy(kv.data(), words(), 2 * n * 8, hipMemcpyDeviceToHost));
+  return NMG_OK;
+}
+
+// The table's used slots over vals (the counts, or the sparse cost cells) as
+// words on the host, none while nothing was inserted since the last reset:
+// compacted on the device into cnt.d_sparse_ck, so only they cross PCIe (the
+// whole table is 12 MB at the default capacity)
+template <class V>
+static int sparse_fetch(nmg_engine* h, const V* vals, std::vector<uint64_t>& kv) {
+  kv.clear();
+  bool any = false;
+  const int rc = sparse_nonempty(h, &any);
+  if (rc || !any) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  SparseWords& sw = h->cnt.d_sparse_ck;
+  HIP_TRY(h, sw.reserve(h->sparse_cap));
+  HIP_TRY(h, sw.compact(h->stream, h->cnt.d_sparse_keys.get(), vals));
+  return sw.download(h, kv);
 }
 
 // Every non-zero (entry, thread, page) cell, entries in id order, each
@@ -294,18 +302,12 @@ int cells_prepare(nmg_engine* h) {
   rc = cprep_layout(h);
   if (rc) return rc;
   lap("meta");
-  std::vector<uint64_t> k;
-  std::vector<uint32_t> v;
-  rc = sparse_download(h, k, v);
+  rc = sparse_download(h, P.sparse_kv);
   if (rc) return rc;
-  P.sparse_kv.resize(2 * k.size());
-  for (size_t i = 0; i < k.size(); i++) {
-    P.sparse_kv[2 * i] = k[i];
-    P.sparse_kv[2 * i + 1] = v[i];
-  }
   lap("sparse");
   P.soff.assign(h->tab.sparse_entries.size(), 0);
-  rc = dense_rows(h, h->tab.cells() && h->E ? h->cnt.d_hist.get() : nullptr, P.rows, !k.empty(), P.soff.data(), lap);
+  rc = dense_rows(h, h->tab.cells() && h->E ? h->cnt.d_hist.get() : nullptr, P.rows,
+                  P.sparse_kv.empty() ? nullptr : &h->cnt.d_sparse_ck, P.soff.data(), lap);
   if (rc) return rc;
   if (lap.on) fprintf(stderr, "cells_prepare: %llu rows\n", (unsigned long long)P.rows.n);
   return NMG_OK;
@@ -346,31 +348,15 @@ int cost_prepare(nmg_engine* h) {
   rc = cprep_layout(h);
   if (rc) return rc;
   c.rows.n = 0;
-  // NMG_COST_SCOPE_ALL: the slots with a non-zero cost compacted on the device
-  // as (key, cost) words -- counted per entry by dense_rows, downloaded for
-  // cost_fill -- unless nothing was inserted since the last reset
-  c.sparse_kv.clear();
+  // NMG_COST_SCOPE_ALL: the slots with a non-zero cost as (key, cost) words --
+  // counted per entry by dense_rows, kept for cost_fill
   c.soff.assign(h->tab.sparse_entries.size(), 0);
-  bool any = false;
-  if (c.d_sparse && h->cnt.d_sparse_keys) {
-    rc = sparse_nonempty(h, &any);
-    if (rc) return rc;
-  }
-  if (any) {
-    HIP_TRY(h, h->cnt.d_sparse_ck.reserve(h->sparse_cap * 2 + 1));
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->cnt.d_sparse_ck + 2 * h->sparse_cap);
-    HIP_TRY(h, hipMemsetAsync(cnt, 0, 8, h->stream));
-    HIP_TRY(h, launch_sparse_compact(h->stream, h->cnt.d_sparse_keys, c.d_sparse.get(), h->sparse_cap,
-                                     h->cnt.d_sparse_ck, cnt));
-    uint64_t n = 0;
-    HIP_TRY(h, hipMemcpyAsync(&n, cnt, 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    c.sparse_kv.resize(2 * n);
-    if (n) HIP_TRY(h, hipMemcpy(c.sparse_kv.data(), h->cnt.d_sparse_ck, 2 * n * 8, hipMemcpyDeviceToHost));
-    any = n != 0;
-  }
+  c.sparse_kv.clear();
+  if (c.d_sparse) rc = sparse_fetch(h, c.d_sparse.get(), c.sparse_kv);
+  if (rc) return rc;
+  const bool any = !c.sparse_kv.empty();
   if (!c.d_cells && !any) return NMG_OK;
-  return dense_rows(h, c.d_cells.get(), c.rows, any, c.soff.data(), Lap{false});
+  return dense_rows(h, c.d_cells.get(), c.rows, any ? &h->cnt.d_sparse_ck : nullptr, c.soff.data(), Lap{false});
 }
 
 // rows[s.n * 4]: the rows D2H (the dense ones; none where the table has no dense cell), the sparse rows placed
@@ -583,95 +569,65 @@ int sparse_nonempty(nmg_engine* h, bool* out) {
   return NMG_OK;
 }
 
-int sparse_download(nmg_engine* h, std::vector<uint64_t>& k, std::vector<uint32_t>& v) {
-  int rc = nmg_synchronize(h);
-  if (rc) return rc;
-  bool any = false;
-  rc = sparse_nonempty(h, &any);
-  if (rc) return rc;
-  if (!any) {
-    k.clear();
-    v.clear();
-    return NMG_OK;
-  }
-  // the used slots compacted on the device (key, count pairs), so only they
-  // cross PCIe (the whole table is 12 MB at the default capacity)
-  HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, h->cnt.d_sparse_ck.reserve(h->sparse_cap * 2 + 1));
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->cnt.d_sparse_ck + 2 * h->sparse_cap);
-  HIP_TRY(h, hipMemsetAsync(cnt, 0, 8, h->stream));
-  HIP_TRY(h, launch_sparse_compact(h->stream, h->cnt.d_sparse_keys, h->cnt.d_sparse_vals, h->sparse_cap, h->cnt.d_sparse_ck, cnt));
-  uint64_t n = 0;
-  HIP_TRY(h, hipMemcpyAsync(&n, cnt, 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  std::vector<uint64_t> kv(2 * n);
-  if (n) HIP_TRY(h, hipMemcpy(kv.data(), h->cnt.d_sparse_ck, 2 * n * 8, hipMemcpyDeviceToHost));
-  k.resize(n);
-  v.resize(n);
-  for (uint64_t i = 0; i < n; i++) {
-    k[i] = kv[2 * i];
-    v[i] = (uint32_t)kv[2 * i + 1];
-  }
-  return NMG_OK;
+int sparse_download(nmg_engine* h, std::vector<uint64_t>& kv) {
+  const int rc = nmg_synchronize(h);
+  return rc ? rc : sparse_fetch(h, h->cnt.d_sparse_vals.get(), kv);
 }
 
 extern "C" int64_t nmg_sparse_count(nmg_engine* h) {
   if (!h || !h->have_table) return NMG_ERR_INVALID;
-  std::vector<uint64_t> k;
-  std::vector<uint32_t> v;
-  int rc = sparse_download(h, k, v);
-  return rc ? rc : (int64_t)k.size();
+  std::vector<uint64_t> kv;
+  int rc = sparse_download(h, kv);
+  return rc ? rc : (int64_t)(kv.size() / 2);
 }
 
 extern "C" int nmg_sparse_export(nmg_engine* h, uint64_t* keys, uint32_t* counts, int64_t n) {
   if (!h || !h->have_table || (n && (!keys || !counts))) return NMG_ERR_INVALID;
-  std::vector<uint64_t> k;
-  std::vector<uint32_t> v;
-  int rc = sparse_download(h, k, v);
+  std::vector<uint64_t> kv;
+  int rc = sparse_download(h, kv);
   if (rc) return rc;
-  if ((int64_t)k.size() != n) return fail(h, NMG_ERR_INVALID, "sparse count mismatch");
+  if ((int64_t)(kv.size() / 2) != n) return fail(h, NMG_ERR_INVALID, "sparse count mismatch");
   // in key order (the device compaction reserves its output slots per wave
   // with an atomic, so its order varies from run to run; keys are unique)
-  std::vector<uint32_t> ord(k.size());
-  for (uint32_t i = 0; i < (uint32_t)ord.size(); i++) ord[i] = i;
-  std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return k[a] < k[b]; });
+  sparse_words_sort(kv);
   for (int64_t i = 0; i < n; i++) {
-    keys[i] = k[ord[i]];
-    counts[i] = v[ord[i]];
+    keys[i] = kv[2 * i];
+    counts[i] = (uint32_t)kv[2 * i + 1];
   }
   return NMG_OK;
 }
 
-extern "C" int nmg_sparse_import(nmg_engine* h, const uint64_t* keys, const uint32_t* counts, int64_t n) {
-  if (h) h->epoch++;
-  // Re-inserts merged (key, count) pairs into an empty table on this rank.
-  if (!h || !h->have_table || (n && (!keys || !counts))) return NMG_ERR_INVALID;
+// nmg_sparse_import over n words (the callers end the results epoch): the table cleared and the
+// words inserted on the device (sparse_add's hash and probing), so only they cross PCIe
+int sparse_import_words(nmg_engine* h, const uint64_t* kv, uint64_t n) {
   if (!h->cnt.d_sparse_keys) return n ? fail(h, NMG_ERR_STATE, "no sparse table") : NMG_OK;
-  if ((uint64_t)n > h->sparse_cap) return fail(h, NMG_ERR_CAPACITY, "sparse table too small");
-  // the table cleared and the pairs inserted on the device (sparse_add's hash
-  // and probing): only the pairs cross PCIe
+  if (n > h->sparse_cap) return fail(h, NMG_ERR_CAPACITY, "sparse table too small");
   HIP_TRY(h, hipSetDevice(h->device));
   int rc = nmg_synchronize(h);
   if (rc) return rc;
-  HIP_TRY(h, h->cnt.d_sparse_ck.reserve(h->sparse_cap * 2 + 1));
+  SparseWords& sw = h->cnt.d_sparse_ck;  // (the words' staging)
+  HIP_TRY(h, sw.reserve(h->sparse_cap));
   HIP_TRY(h, hipMemsetAsync(h->cnt.d_sparse_keys, 0xff, h->sparse_cap * 8, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->cnt.d_sparse_vals, 0, h->sparse_cap * 4, h->stream));
   // (the slots move: the sparse cost cells start again -- cost cells are not merged across ranks)
   if (h->cost.d_sparse) HIP_TRY(h, hipMemsetAsync(h->cost.d_sparse, 0, h->sparse_cap * 8, h->stream));
   if (n) {
-    std::vector<uint64_t> kv(2 * (size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-      kv[2 * i] = keys[i];
-      kv[2 * i + 1] = counts[i];
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->cnt.d_sparse_ck, kv.data(), kv.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, launch_sparse_insert(h->stream, h->cnt.d_sparse_keys, h->cnt.d_sparse_vals, h->sparse_cap, h->cnt.d_sparse_ck,
-                                    (uint64_t)n));
+    HIP_TRY(h, hipMemcpyAsync(sw.words(), kv, 2 * n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, launch_sparse_insert(h->stream, h->cnt.d_sparse_keys, h->cnt.d_sparse_vals, h->sparse_cap, sw.words(), n));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // (kv is pageable)
   }
   const uint32_t one = 1;  // imported cells: the next reset must clear the table
   HIP_TRY(h, hipMemcpy(h->cnt.d_sparse_dirty + (h->nreset & 1), &one, 4, hipMemcpyHostToDevice));
   return NMG_OK;
+}
+
+extern "C" int nmg_sparse_import(nmg_engine* h, const uint64_t* keys, const uint32_t* counts, int64_t n) {
+  if (h) h->epoch++;
+  if (!h || !h->have_table || (n && (!keys || !counts))) return NMG_ERR_INVALID;
+  std::vector<uint64_t> kv;  // (the import refuses the other n without reading a word)
+  if (h->cnt.d_sparse_keys && (uint64_t)n <= h->sparse_cap)
+    for (int64_t i = 0; i < n; i++) kv.insert(kv.end(), {keys[i], (uint64_t)counts[i]});
+  return sparse_import_words(h, kv.data(), (uint64_t)n);
 }
 
 extern "C" int nmg_set_buffer_counts(nmg_engine* h, uint32_t nb_buffers, const uint32_t* nb_samples,
@@ -710,7 +666,7 @@ static int snap_alloc(nmg_engine* h) {
   HIP_TRY(h, S.d_found.reserve(1));
   HIP_TRY(h, S.d_bufcnt.reserve(2 * nb + 1));
   HIP_TRY(h, S.d_rows.reserve(rows + 1));
-  if (h->cnt.d_sparse_keys) HIP_TRY(h, S.d_ck.reserve(2 * h->sparse_cap + 1));
+  if (h->cnt.d_sparse_keys) HIP_TRY(h, S.d_ck.reserve(h->sparse_cap));
   // pinned host copies (the rows grow on demand in nmg_results_end)
   HIP_TRY(h, S.h_sum.reserve(kCwBase));
   HIP_TRY(h, S.h_max.reserve(max64_words()));
@@ -744,18 +700,12 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
   const uint64_t E = h->E, nb = h->descs.size(), nsent = h->tab.sparse_entries.size();
   hipStream_t st = h->stream;
   CellLayout& L = S.lay;
-  if (L.meta_dirty) {  // (the table's cell layout: uploaded once per table, through the
-                       // pinned staging on the engine stream -- begin never waits for it)
-    // with the sparse entries as this table has them: nmg_results_end places
-    // the sparse rows with these, whatever table the engine holds by then
-    std::vector<uint32_t> np;
-    cell_layout_host(h, np, S.sent_entry);
-    rc = stage_h2d(h, L.d_base, h->tab.hist_base.data(), E * 8);
-    if (!rc) rc = stage_h2d(h, L.d_np, np.data(), E * 4);
-    if (!rc) rc = stage_h2d(h, L.d_sent, h->tab.sparse_entries.data(), nsent * 4);
-    if (rc) return rc;
-    L.meta_dirty = false;
-  }
+  // the table's cell layout through the pinned staging on the engine stream
+  // (begin never waits for it), with the sparse entries as this table has them:
+  // nmg_results_end places the sparse rows with these, whatever table the
+  // engine holds by then
+  rc = layout_upload(h, L, S.sent_entry, stage_h2d);
+  if (rc) return rc;
   // the device snapshot, behind the enqueued analyses
   HIP_TRY(h, hipMemcpyAsync(S.d_sum, h->cnt.d_sum64, kCwBase * 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(h, hipMemcpyAsync(S.d_min, h->cnt.d_min64, first_index(E) * 8, hipMemcpyDeviceToDevice, st));
@@ -767,25 +717,17 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
   if (h->d_found) HIP_TRY(h, hipMemcpyAsync(S.d_found, h->d_found, 8, hipMemcpyDeviceToDevice, st));
   else HIP_TRY(h, hipMemsetAsync(S.d_found, 0, 8, st));
   if (E) HIP_TRY(h, launch_objcw_aos(st, h->cnt.d_sum64 + kCwBase, E, S.d_objcw));
-  // page-cell rows: per-entry counts (dense, then the sparse table's), their
-  // exclusive scan, the dense rows; the sparse ones are placed by the host
-  unsigned long long* nsp = S.d_ck ? reinterpret_cast<unsigned long long*>(S.d_ck + 2 * h->sparse_cap) : nullptr;
+  // page-cell rows, the synchronous getters' pass without a wait: per-entry
+  // counts (dense, then the sparse table's from its words compacted here),
+  // their exclusive scan, the dense rows; the sparse ones are placed by the host
+  const uint32_t* hist = h->tab.cells() ? h->cnt.d_hist.get() : nullptr;
+  const SparseWords* sw = h->cnt.d_sparse_keys ? &S.d_ck : nullptr;  // (d_ck may outlive a table that had sparse cells)
+  if (sw) HIP_TRY(h, sw->compact(st, h->cnt.d_sparse_keys.get(), h->cnt.d_sparse_vals.get()));
   if (E) {
-    if (h->tab.cells())
-      HIP_TRY(h, launch_cells_count(st, h->cnt.d_hist, h->tab.cells(), h->T, L.d_base, L.d_np, (uint32_t)E, L.d_cnt));
-    else
-      HIP_TRY(h, hipMemsetAsync(L.d_cnt, 0, E * 4, st));
-    if (nsp) {
-      HIP_TRY(h, hipMemsetAsync(nsp, 0, 8, st));
-      HIP_TRY(h, launch_sparse_compact(st, h->cnt.d_sparse_keys, h->cnt.d_sparse_vals, h->sparse_cap, S.d_ck, nsp));
-      HIP_TRY(h, launch_cells_sparse_count(st, S.d_ck, nsp, h->sparse_cap, L.d_sent, (uint32_t)nsent, L.d_base,
-                                           L.d_cnt));
-    }
+    HIP_TRY(h, pass_count(h, L, hist, sw));
     HIP_TRY(h, launch_scan_u32(st, L.d_cnt, E, L.d_off, L.d_part));
-    if (h->tab.cells())
-      HIP_TRY(h, launch_cells_emit(st, h->cnt.d_hist, h->tab.cells(), h->T, L.d_base, L.d_np, (uint32_t)E, L.d_off,
-                                   S.d_rows));
-    HIP_TRY(h, launch_gather_off(st, L.d_off, L.d_sent, (uint32_t)nsent, L.d_soff));
+    if (hist) HIP_TRY(h, pass_emit(h, L, hist, S.d_rows.get()));
+    HIP_TRY(h, pass_soff(h, L));
   } else {
     HIP_TRY(h, hipMemsetAsync(L.d_off, 0, 8, st));
   }
@@ -799,7 +741,7 @@ extern "C" int nmg_results_begin(nmg_engine* h) {
   if (nb) HIP_TRY(h, hipMemcpyAsync(S.h_bufcnt, S.d_bufcnt, 2 * nb * 4, hipMemcpyDeviceToHost, cs));
   HIP_TRY(h, hipMemcpyAsync(S.h_small, S.d_found, 8, hipMemcpyDeviceToHost, cs));
   HIP_TRY(h, hipMemcpyAsync(S.h_small + 1, L.d_off + E, 8, hipMemcpyDeviceToHost, cs));
-  if (nsp) HIP_TRY(h, hipMemcpyAsync(S.h_small + 2, nsp, 8, hipMemcpyDeviceToHost, cs));
+  if (sw) HIP_TRY(h, hipMemcpyAsync(S.h_small + 2, sw->count(), 8, hipMemcpyDeviceToHost, cs));
   else S.h_small[2] = 0;
   if (E) HIP_TRY(h, hipMemcpyAsync(S.h_objcw, S.d_objcw, E * 32, hipMemcpyDeviceToHost, cs));
   if (nsent) HIP_TRY(h, hipMemcpyAsync(S.h_soff, L.d_soff, nsent * 8, hipMemcpyDeviceToHost, cs));
@@ -829,8 +771,9 @@ extern "C" int nmg_results_end(nmg_engine* h, nmg_results_view* out) {
     HIP_TRY(h, hipMemcpy(S.h_rows, S.d_rows, nrows * 16, hipMemcpyDeviceToHost));
   }
   if (nspc) {  // the sparse cells, each entry's in (thread, page) order at its rows
-    std::vector<uint64_t> kv(2 * nspc);
-    HIP_TRY(h, hipMemcpy(kv.data(), S.d_ck, 2 * nspc * 8, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> kv;
+    const int rc = S.d_ck.download(h, kv, &nspc);
+    if (rc) return rc;
     place_sparse_rows<uint32_t>(kv.data(), nspc, S.sent_entry, S.h_soff, S.h_rows);
   }
   memset(out, 0, sizeof(*out));

@@ -316,6 +316,35 @@ def test_page_cells_with_sparse_entries(tiny, kind):
     assert (rc1, rc2) == (OK, OK) and same(a, b) and same(a, want)
     rc, _ = get(eng, "cells", n1 - 1)
     assert rc == INVALID and "row count mismatch" in last_error(eng)
+    # the results snapshot of the same engine: the same rows
+    eng.results_begin()
+    snap = np.array(eng.results_end()[7])  # (cells [nb_cells, 4])
+    assert snap.shape[0] == want.shape[0] and same(snap, want)
+    # the exported sparse cells: keys ascending, and decoded (sparse idx:22 | thread:10 | page:32; sparse idx ->
+    # entry in id order) exactly the oracle's rows of the sparse entries
+    keys, vals = eng.sparse_export()
+    assert keys.dtype == np.uint64 and vals.dtype == np.uint32 and np.all(keys[1:] > keys[:-1])
+    sparse_ids = np.flatnonzero(~dense_model(tiny.rp.table, T, budget))
+    assert (keys >> np.uint64(42) < sparse_ids.shape[0]).all()
+    decoded = np.stack([sparse_ids[(keys >> np.uint64(42)).astype(np.int64)], (keys >> np.uint64(32)) & np.uint64(0x3ff),
+                        keys & np.uint64(0xffffffff), vals], axis=1).astype(np.uint32)
+    assert same(decoded, want[np.isin(want[:, 0], sparse_ids)])
+    eng.close()
+
+
+def test_snapshot_of_an_empty_table(tiny):
+    """E = 0: the snapshot has no cell, and its counts are the synchronous getters'."""
+    eng = run(engine(tiny.rp, table=ObjectTable.empty(), products=()))
+    g, ns, nf = eng.global_counters()
+    bs, bf = eng.buffer_counts()
+    assert (ns, nf) == (128, 0) and bs.tolist() == [64, 64]
+    assert count(eng, "cells") == 0
+    eng.results_begin()
+    got = eng.results_end()
+    assert got[7].shape == (0, 4)  # nb_cells == 0
+    assert np.array_equal(got[0], g) and (got[1], got[2]) == (ns, nf)
+    assert np.array_equal(np.array(got[3]), bs) and np.array_equal(np.array(got[4]), bf)
+    assert got[5].shape[0] == 0 and got[6].shape[0] == 0  # no entry
     eng.close()
 
 
