@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <set>
 #include <string>
 #include <unordered_map>
@@ -78,6 +79,7 @@ struct RipKeyHash {
 class Registry {
  public:
   explicit Registry(const nmg_object_meta* meta) : meta_(meta) {}
+  const nmg_object_meta* meta() const { return meta_; }
 
   // find_call_site (mem_analyzer.c:1302-1331)
   int64_t find(uint32_t e) const {
@@ -151,6 +153,16 @@ class Registry {
 // int-truncated running minimum back to uint64_t (mem_analyzer.c:1544-1547)
 inline uint64_t trunc_key(uint64_t x) { return (uint64_t)(int64_t)(int32_t)(uint32_t)x; }
 
+// the first position >= from of the min tree whose value < m, or -1
+int64_t first_below(const std::vector<uint64_t>& tree, int64_t node, int64_t lo, int64_t hi, int64_t from,
+                    uint64_t m) {
+  if (hi < from || tree[node] >= m) return -1;
+  if (lo == hi) return lo;
+  const int64_t mid = (lo + hi) / 2;
+  const int64_t r = first_below(tree, 2 * node, lo, mid, from, m);
+  return r >= 0 ? r : first_below(tree, 2 * node + 1, mid + 1, hi, from, m);
+}
+
 // Returns the final list order (indices into sites), head first.
 std::vector<int64_t> sort_sites(const std::vector<Site>& sites) {
   const int64_t n = (int64_t)sites.size();
@@ -180,16 +192,6 @@ std::vector<int64_t> sort_sites(const std::vector<Site>& sites) {
     tree[i] = kDead;
     for (i >>= 1; i >= 1; i >>= 1) tree[i] = std::min(tree[2 * i], tree[2 * i + 1]);
   };
-  // first position >= from whose value < m, or -1
-  std::function<int64_t(int64_t, int64_t, int64_t, int64_t, uint64_t)> first_below;
-  first_below = [&](int64_t node, int64_t lo, int64_t hi, int64_t from, uint64_t m) -> int64_t {
-    if (hi < from || tree[node] >= m) return -1;
-    if (lo == hi) return lo;
-    int64_t mid = (lo + hi) / 2;
-    int64_t r = first_below(2 * node, lo, mid, from, m);
-    if (r >= 0) return r;
-    return first_below(2 * node + 1, mid + 1, hi, from, m);
-  };
   std::vector<int64_t> removal;
   removal.reserve(n);
   std::vector<char> alive(n, 1);
@@ -200,7 +202,7 @@ std::vector<int64_t> sort_sites(const std::vector<Site>& sites) {
     uint64_t m = trunc_key(sites[n - 1 - head].read_weight);
     int64_t from = head;  // the head is compared against itself too
     for (;;) {
-      int64_t q = first_below(1, 0, sz - 1, from, m);
+      int64_t q = first_below(tree, 1, 0, sz - 1, from, m);
       if (q < 0) break;
       pick = q;
       m = trunc_key(sites[n - 1 - q].read_weight);
@@ -255,21 +257,30 @@ void print_counters(FILE* f, const nmg_mem_counters* counters) {
   }
 }
 
-// Per-site page x thread matrix (__plot_counters input): dense unless huge.
-struct SiteHist {
+// A site's page x thread matrix (__plot_counters, mem_analyzer.c:1557-1585):
+// site->mem_info.buffer_size / 4096 + 1 rows of next_thread_rank cells, each
+// the sum of the site's objects' cells; their pages past its rows, and threads
+// that do not exist, are dropped.  A stack site has none, nor has a stack
+// entry (_dump_call_site, mem_sampling.c:775-808).
+struct SiteShape {
   uint64_t rows = 0;
   uint32_t T = 0;
+  SiteShape() {}
+  SiteShape(const Site& s, uint32_t t)
+      : rows(s.mem_type == kMemTypeStack ? 0 : s.mem_info_buffer_size / kPageSize + 1), T(t) {}
+  bool holds(uint64_t page, uint64_t th) const { return page < rows && th < T; }
+};
+
+// The matrix of the page counts: dense unless huge.
+struct SiteHist : SiteShape {
   bool dense = true;
   std::vector<uint32_t> cells;                    // [page][thread]
   std::unordered_map<uint64_t, uint32_t> sparse;  // page * T + thread
-  void init(uint64_t r, uint32_t t) {
-    rows = r;
-    T = t;
-    dense = r * t <= (1ull << 26);
-    if (dense) cells.assign(r * t, 0);
+  explicit SiteHist(const SiteShape& shape) : SiteShape(shape), dense(rows * T <= (1ull << 26)) {
+    if (dense) cells.assign(rows * T, 0);
   }
   void add(uint64_t page, uint32_t th, uint32_t v) {
-    if (page >= rows || th >= T) return;
+    if (!holds(page, th)) return;
     if (dense) cells[page * T + th] += v;
     else sparse[page * T + th] += v;
   }
@@ -317,6 +328,65 @@ T load(const uint8_t* p) {
   return v;
 }
 
+// A file closed when its owner goes; stdout, which write_report may be given to
+// write to, is flushed instead.
+struct FileClose {
+  void operator()(FILE* f) const { f == stdout ? fflush(f) : fclose(f); }
+};
+typedef std::unique_ptr<FILE, FileClose> File;
+
+// settings.output_dir ("." by default), made here as get_log_dir makes it
+// (mem_intercept.c:402-409): where every file but write_report's stdout goes.
+struct OutDir {
+  std::string dir;
+  OutDir() {}  // (none yet)
+  explicit OutDir(const nmg_report_options* opts) : dir(opts && opts->output_dir ? opts->output_dir : ".") {
+    mkdir(dir.c_str(), S_IRWXU);
+  }
+  File open(const std::string& base, std::string& err) const {
+    const std::string path = dir + "/" + base;
+    File f(fopen(path.c_str(), "w"));
+    if (!f) err = "cannot open " + path;
+    return f;
+  }
+};
+std::string site_file(const char* kind, uint32_t id) {
+  return std::string("callsite_") + kind + "_" + std::to_string((int)id) + ".dat";
+}
+
+// One matrix file: `shape.rows` lines of `shape.T` cells, in that order;
+// cell(buf, size, page, thread) formats one and returns its length.
+template <class Cell>
+void write_matrix(FILE* f, const SiteShape& shape, Cell&& cell) {
+  std::string line;
+  char buf[32];
+  for (uint64_t pg = 0; pg < shape.rows; pg++) {
+    line.clear();
+    for (uint32_t th = 0; th < shape.T; th++) line.append(buf, cell(buf, sizeof(buf), pg, th));
+    line.push_back('\n');
+    fwrite(line.data(), 1, line.size(), f);
+  }
+}
+
+// (key, value) cells in any order -> ascending keys, each once, the values of equal keys summed
+typedef std::vector<std::pair<uint64_t, uint64_t>> KeyedCells;
+void sum_runs(KeyedCells& l) {
+  std::sort(l.begin(), l.end());
+  size_t m = 0;
+  for (const auto& c : l)
+    if (m && l[m - 1].first == c.first) l[m - 1].second += c.second;
+    else l[m++] = c;
+  l.resize(m);
+}
+
+// entry e's rows of the n (entry, thread, page, count) rows sorted by entry: [begin[e], begin[e + 1])
+std::vector<int64_t> entry_ranges(const uint32_t* cells, int64_t n, uint32_t E) {
+  std::vector<int64_t> begin((size_t)E + 1, 0);
+  for (int64_t i = 0; i < n; i++) begin[cells[4 * i] + 1]++;
+  for (uint32_t e = 0; e < E; e++) begin[e + 1] += begin[e];
+  return begin;
+}
+
 // The unmatched-sample log header (mem_sampling.c:608-638): the traced
 // process's maps file copied by `while (!feof) { fgets(line, 1024); fprintf }`,
 // which repeats the last line when the file ends with a newline.
@@ -360,13 +430,11 @@ const nmg_module* find_module(const std::vector<const nmg_module*>& mods, uint64
 // USE_HASHTABLE (:23) print_object_summary_from_list ignores its list
 // argument, so the second call, meant for past_mem_list, prints mem_list
 // again (quirk Q20: every row twice).
-int write_object_summary(const std::string& path, const nmg_host_results* r, const nmg_object_meta* meta,
+int write_object_summary(const OutDir& dir, const nmg_host_results* r, const nmg_object_meta* meta,
                          const nmg_report_options* opts, std::string& err) {
-  FILE* f = fopen(path.c_str(), "w");
-  if (!f) {
-    err = "cannot open " + path;
-    return NMG_ERR_IO;
-  }
+  const File file = dir.open("all_memory_objects.dat", err);
+  if (!file) return NMG_ERR_IO;
+  FILE* f = file.get();
   std::vector<const nmg_module*> mods;
   for (uint32_t i = 0; opts->modules && i < opts->nb_modules; i++) mods.push_back(&opts->modules[i]);
   std::sort(mods.begin(), mods.end(), [](const nmg_module* a, const nmg_module* b) { return a->lo < b->lo; });
@@ -413,17 +481,18 @@ int write_object_summary(const std::string& path, const nmg_host_results* r, con
   }
   for (int pass = 0; pass < 2; pass++)
     for (const std::string& row : rows) fwrite(row.data(), 1, row.size(), f);
-  fclose(f);
   return NMG_OK;
 }
 
 // The call sites of the results r (settings.match_samples on), as ma_finalize
 // leaves them: created in the analysis order of each object's first matched
-// sample, then every object that reaches update_call_sites attached.  The one
-// registry of write_report and write_timeline: a site's id is the same in both.
-template <class Phase>
-int fill_registry(Registry& reg, const nmg_host_results* r, const nmg_object_meta* meta, bool online,
-                  std::string& err, Phase&& phase) {
+// sample, then every object that reaches update_call_sites attached; none with
+// match_samples off.  The one registry of every writer and of the placement
+// groups: a site's id is the same in all.  phase: write_report's timing marks.
+int site_registry(Registry& reg, const nmg_host_results* r, bool online, std::string& err,
+                  const std::function<void(const char*)>& phase = [](const char*) {}) {
+  if (!r->match_samples) return NMG_OK;
+  const nmg_object_meta* meta = reg.meta();
   const uint32_t E = r->nb_entries;
   std::vector<uint32_t> matched;
   for (uint32_t e = 0; e < E; e++)
@@ -464,53 +533,41 @@ int fill_registry(Registry& reg, const nmg_host_results* r, const nmg_object_met
   return NMG_OK;
 }
 
+// the site whose per-site files take entry e's samples and cells, or -1: a
+// stack entry has none, nor has an entry without matched samples
+int64_t file_site(const Registry& reg, uint32_t e) {
+  return reg.meta()[e].mem_type == kMemTypeStack ? -1 : reg.find(e);
+}
+
 }  // namespace
 
 // callsite_timeline_<id>.dat per call site with a non-zero cell (the format is
 // in include/numamma_gpu.h).  rows: (entry, bin, thread, row, count), any
 // order; a site's cell sums its objects' cells, as update_call_sites sums
-// their page blocks.  Stack objects have no per-site files (_dump_call_site,
-// mem_sampling.c:775-808).
+// their page blocks.
 int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
                    const nmg_timeline_options* tl, const uint32_t* rows, int64_t n, std::string& err) {
-  const bool online = opts && opts->online;
   Registry reg(meta);
-  if (r->match_samples) {
-    const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
-    if (rc) return rc;
-  }
+  if (const int rc = site_registry(reg, r, opts && opts->online, err)) return rc;
   // per site: (bin, thread, row) key and count of every row of its objects
-  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> per(reg.sites.size());
+  std::vector<KeyedCells> per(reg.sites.size());
   for (int64_t i = 0; i < n; i++) {
     const uint32_t* q = rows + 5 * i;
-    if (!q[4] || meta[q[0]].mem_type == kMemTypeStack) continue;
-    const int64_t si = reg.find(q[0]);
-    if (si < 0) continue;  // (an entry without matched samples has no cells)
-    per[si].push_back({(uint64_t(q[1]) << 42) | (uint64_t(q[2]) << 32) | q[3], q[4]});
+    const int64_t si = q[4] ? file_site(reg, q[0]) : -1;
+    if (si >= 0) per[si].push_back({(uint64_t(q[1]) << 42) | (uint64_t(q[2]) << 32) | q[3], q[4]});
   }
-  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
-  mkdir(dir, S_IRWXU);
+  const OutDir dir(opts);
   for (size_t si = 0; si < per.size(); si++) {
-    auto& l = per[si];
-    if (l.empty()) continue;
-    std::sort(l.begin(), l.end());
-    char fn[4096];
-    snprintf(fn, sizeof(fn), "%s/callsite_timeline_%d.dat", dir, (int)reg.sites[si].id);
-    FILE* f = fopen(fn, "w");
-    if (!f) {
-      err = std::string("cannot open ") + fn;
-      return NMG_ERR_IO;
+    if (per[si].empty()) continue;
+    sum_runs(per[si]);
+    const File f = dir.open(site_file("timeline", reg.sites[si].id), err);
+    if (!f) return NMG_ERR_IO;
+    fprintf(f.get(), "#thread_rank timestamp offset count\n");
+    for (const auto& c : per[si]) {
+      const uint64_t bin = c.first >> 42, th = (c.first >> 32) & 0x3ff, row = c.first & 0xffffffffull;
+      fprintf(f.get(), "%" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", th, tl->t0 + (bin << tl->bin_shift),
+              row << (12 + tl->row_shift), c.second);
     }
-    fprintf(f, "#thread_rank timestamp offset count\n");
-    for (size_t i = 0; i < l.size();) {
-      const uint64_t key = l[i].first;
-      uint64_t cnt = 0;
-      for (; i < l.size() && l[i].first == key; i++) cnt += l[i].second;
-      const uint64_t bin = key >> 42, th = (key >> 32) & 0x3ff, row = key & 0xffffffffull;
-      fprintf(f, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", th, tl->t0 + (bin << tl->bin_shift),
-              row << (12 + tl->row_shift), cnt);
-    }
-    fclose(f);
   }
   return NMG_OK;
 }
@@ -518,56 +575,31 @@ int write_timeline(const nmg_host_results* r, const nmg_object_meta* meta, const
 // callsite_cost_<id>.dat per call site with a non-zero cell inside its rows
 // (the format is in include/numamma_gpu.h): the matrix of
 // callsite_counters_<id>.dat with the cost cells in it.  rows: (entry, thread,
-// page, value), any order; a site's cell sums its objects' cells, pages past
-// the site's rows dropped, as SiteHist::add drops them.
+// page, value), any order; a site's cell sums its objects' cells (SiteShape).
 int write_page_cost(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
                     const uint64_t* rows, int64_t n, std::string& err) {
-  const bool online = opts && opts->online;
-  const uint64_t T = r->nb_threads;
+  const uint32_t T = r->nb_threads;
   Registry reg(meta);
-  if (r->match_samples) {
-    const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
-    if (rc) return rc;
-  }
-  // per site: (page * T + thread, value) of every row of its objects inside its rows
-  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> per(reg.sites.size());
+  if (const int rc = site_registry(reg, r, opts && opts->online, err)) return rc;
+  // per site: (page * T + thread, value) of every row of its objects inside its matrix
+  std::vector<KeyedCells> per(reg.sites.size());
   for (int64_t i = 0; i < n; i++) {
     const uint64_t* q = rows + 4 * i;
-    if (!q[3] || meta[q[0]].mem_type == kMemTypeStack) continue;
-    const int64_t si = reg.find((uint32_t)q[0]);
-    if (si < 0) continue;  // (an entry without matched samples has no cells)
-    const Site& s = reg.sites[si];
-    if (s.mem_type == kMemTypeStack || q[2] >= s.mem_info_buffer_size / kPageSize + 1) continue;
-    per[si].push_back({q[2] * T + q[1], q[3]});
+    const int64_t si = q[3] ? file_site(reg, (uint32_t)q[0]) : -1;
+    if (si >= 0 && SiteShape(reg.sites[si], T).holds(q[2], q[1])) per[si].push_back({q[2] * T + q[1], q[3]});
   }
-  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
-  mkdir(dir, S_IRWXU);
-  std::string line;
-  char cell[32];
+  const OutDir dir(opts);
   for (size_t si = 0; si < per.size(); si++) {
-    auto& l = per[si];
+    const KeyedCells& l = per[si];
     if (l.empty()) continue;
-    std::sort(l.begin(), l.end());
-    char fn[4096];
-    snprintf(fn, sizeof(fn), "%s/callsite_cost_%d.dat", dir, (int)reg.sites[si].id);
-    FILE* f = fopen(fn, "w");
-    if (!f) {
-      err = std::string("cannot open ") + fn;
-      return NMG_ERR_IO;
-    }
-    const uint64_t nrows = reg.sites[si].mem_info_buffer_size / kPageSize + 1;
-    size_t i = 0;
-    for (uint64_t pg = 0; pg < nrows; pg++) {
-      line.clear();
-      for (uint64_t th = 0; th < T; th++) {
-        uint64_t v = 0;
-        for (; i < l.size() && l[i].first == pg * T + th; i++) v += l[i].second;
-        line.append(cell, snprintf(cell, sizeof(cell), "\t%" PRIu64, v));
-      }
-      line.push_back('\n');
-      fwrite(line.data(), 1, line.size(), f);
-    }
-    fclose(f);
+    sum_runs(per[si]);
+    const File f = dir.open(site_file("cost", reg.sites[si].id), err);
+    if (!f) return NMG_ERR_IO;
+    size_t i = 0;  // the cells come in the matrix's order
+    write_matrix(f.get(), SiteShape(reg.sites[si], T), [&](char* buf, size_t size, uint64_t pg, uint32_t th) {
+      const uint64_t v = i < l.size() && l[i].first == pg * T + th ? l[i++].second : 0;
+      return snprintf(buf, size, "\t%" PRIu64, v);
+    });
   }
   return NMG_OK;
 }
@@ -635,10 +667,7 @@ int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta
                           const uint64_t* npages, const uint8_t* dense, PlaceGroups& g,
                           std::vector<PlaceSite>& sites, std::string& err, bool all) {
   Registry reg(meta);
-  if (r->match_samples) {
-    const int rc = fill_registry(reg, r, meta, online, err, [](const char*) {});
-    if (rc) return rc;
-  }
+  if (const int rc = site_registry(reg, r, online, err)) return rc;
   constexpr uint32_t kGlobalSymbol = 1, kDynamicAllocation = 3;  // enum mem_type, mem_analyzer.h:58-64
   for (const Site& s : reg.sites) {  // (creation order: ascending id)
     std::string ident;
@@ -651,7 +680,7 @@ int placement_site_groups(const nmg_host_results* r, const nmg_object_meta* meta
       continue;
     }
     const size_t g0 = g.gid.size();
-    g.add(s.id, s.mem_info_buffer_size / kPageSize + 1, s.objects, npages, dense, all);
+    g.add(s.id, SiteShape(s, 0).rows, s.objects, npages, dense, all);
     if (g.gid.size() != g0) sites.push_back(PlaceSite{s.id, s.caller, ident, s.buffer_size});
   }
   return NMG_OK;
@@ -669,89 +698,74 @@ void placement_blocks_host(const PlaceGroups& g, const PlaceMap& m, const uint32
       used.push_back(n);
     }
   const size_t U = used.size();
-  std::vector<int64_t> cell_begin((size_t)nb_entries + 1, 0);
-  for (int64_t i = 0; i < nb_cells; i++) cell_begin[cells[4 * i] + 1]++;
-  for (uint32_t e = 0; e < nb_entries; e++) cell_begin[e + 1] += cell_begin[e];
+  const std::vector<int64_t> cell_begin = entry_ranges(cells, nb_cells, nb_entries);
+  // A group's pages in ascending order, each with its dominant node and that
+  // node's count: a page that qualifies starts a row (gid, node, first, last,
+  // count) or extends the last one; one that does not is skipped and closes
+  // nothing, so a run goes on across it.
+  bool open = false;
+  uint32_t open_gid = 0, prev = 0;
+  auto append_block = [&](uint32_t gid, uint64_t page, uint32_t node, uint64_t best) {
+    if (best <= m.D) return;
+    if (open && gid == open_gid && node == prev) {
+      rows[rows.size() - 2] = page;
+      rows[rows.size() - 1] += best;
+    } else {
+      const uint64_t row[5] = {gid, node, page, page, best};
+      rows.insert(rows.end(), row, row + 5);
+      open = true, open_gid = gid, prev = node;
+    }
+  };
   std::vector<uint64_t> c;
-  std::vector<std::pair<uint64_t, uint64_t>> list;  // a huge group's cells: (page << 6 | node, count)
+  KeyedCells list;  // a huge group's cells: (page << 6 | node, count)
   for (size_t gi = 0; gi < g.gid.size(); gi++) {
-    const uint32_t R = g.rows[gi];
-    if (g.huge[gi]) {
-      // the touched pages only: the members' cells gathered, sorted by (page,
-      // node), equal keys summed, then the walk below over the pages present
-      list.clear();
+    // a group's cells inside its members' pages: fn(page, thread, count)
+    auto for_cells = [&](auto&& fn) {
       for (uint32_t k = g.m_off[gi]; k < g.m_off[gi + 1]; k++) {
         const uint32_t e = g.m_entry[k], np = g.m_np[k];
         for (int64_t i = cell_begin[e]; i < cell_begin[e + 1]; i++) {
           const uint32_t* q = cells + 4 * i;
-          if (q[2] < np && q[1] < T && q[3]) list.push_back({(uint64_t(q[2]) << 6) | m.node[q[1]], q[3]});
+          if (q[2] < np && q[1] < T) fn(q[2], q[1], q[3]);
         }
       }
-      std::sort(list.begin(), list.end());
-      bool open = false;
-      uint32_t prev = 0;
+    };
+    if (g.huge[gi]) {
+      // the touched pages only: the members' cells summed by (page, node), then
+      // the pages present (nodes ascending; strict: the lowest on a tie)
+      list.clear();
+      for_cells([&](uint32_t page, uint32_t th, uint32_t n) {
+        if (n) list.push_back({(uint64_t(page) << 6) | m.node[th], n});
+      });
+      sum_runs(list);
       for (size_t i = 0; i < list.size();) {
         const uint64_t page = list[i].first >> 6;
         uint64_t best = 0;
         uint32_t node = 0;
-        while (i < list.size() && list[i].first >> 6 == page) {
-          const uint64_t key = list[i].first;
-          uint64_t sum = 0;
-          for (; i < list.size() && list[i].first == key; i++) sum += list[i].second;
-          if (sum > best) best = sum, node = (uint32_t)(key & 63);  // (nodes ascending; strict: the lowest on a tie)
-        }
-        if (best <= m.D) continue;
-        if (!open || node != prev) {
-          const uint64_t row[5] = {g.gid[gi], node, page, page, best};
-          rows.insert(rows.end(), row, row + 5);
-          open = true;
-          prev = node;
-        } else {
-          rows[rows.size() - 2] = page;
-          rows[rows.size() - 1] += best;
-        }
+        for (; i < list.size() && list[i].first >> 6 == page; i++)
+          if (list[i].second > best) best = list[i].second, node = (uint32_t)(list[i].first & 63);
+        append_block(g.gid[gi], page, node, best);
       }
       continue;
     }
+    const uint32_t R = g.rows[gi];
     c.assign((size_t)R * U, 0);
-    for (uint32_t k = g.m_off[gi]; k < g.m_off[gi + 1]; k++) {
-      const uint32_t e = g.m_entry[k], np = g.m_np[k];
-      for (int64_t i = cell_begin[e]; i < cell_begin[e + 1]; i++) {
-        const uint32_t* q = cells + 4 * i;
-        if (q[2] < np && q[1] < T) c[(size_t)q[2] * U + col[q[1]]] += q[3];
-      }
-    }
-    bool open = false;
-    uint32_t prev = 0;
+    for_cells([&](uint32_t page, uint32_t th, uint32_t n) { c[(size_t)page * U + col[th]] += n; });
     for (uint32_t p = 0; p < R; p++) {
       uint64_t best = 0;
       uint32_t node = 0;
       for (size_t u = 0; u < U; u++)
         if (c[(size_t)p * U + u] > best) best = c[(size_t)p * U + u], node = used[u];  // (strict: the lowest node on a tie)
-      if (best <= m.D) continue;
-      if (!open || node != prev) {
-        const uint64_t row[5] = {g.gid[gi], node, p, p, best};
-        rows.insert(rows.end(), row, row + 5);
-        open = true;
-        prev = node;
-      } else {
-        rows[rows.size() - 2] = p;
-        rows[rows.size() - 1] += best;
-      }
+      append_block(g.gid[gi], p, node, best);
     }
   }
 }
 
 int write_blocks(const std::vector<PlaceSite>& sites, const uint64_t* rows, int64_t n,
                  const nmg_report_options* opts, std::string& err) {
-  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
-  mkdir(dir, S_IRWXU);
-  const std::string path = std::string(dir) + "/blocks.dat";
-  FILE* f = fopen(path.c_str(), "w");
-  if (!f) {
-    err = "cannot open " + path;
-    return NMG_ERR_IO;
-  }
+  const OutDir dir(opts);
+  File file = dir.open("blocks.dat", err);
+  if (!file) return NMG_ERR_IO;
+  FILE* f = file.get();
   int64_t i = 0;
   for (const PlaceSite& s : sites) {  // (ascending id, as the rows' groups)
     while (i < n && rows[5 * i] < s.id) i++;
@@ -766,369 +780,325 @@ int write_blocks(const std::vector<PlaceSite>& sites, const uint64_t* rows, int6
     fprintf(f, "end_block\n");
   }
   const bool bad = ferror(f) != 0;
-  if (fclose(f) != 0 || bad) {
-    err = "cannot write " + path;
+  if (fclose(file.release()) != 0 || bad) {
+    err = "cannot write " + dir.dir + "/blocks.dat";
     return NMG_ERR_IO;
   }
   return NMG_OK;
 }
 
-int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
-                 const char* stdout_path, std::string& err, const DumpInput* dump, const uint64_t* found_override) {
-  // NMG_REPORT_TIMING=1: phase times on stderr
-  const bool timing = getenv("NMG_REPORT_TIMING") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto phase = [&](const char* name) {
-    if (!timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "nmg_report: %s %.3f s\n", name, std::chrono::duration<double>(t - t_last).count());
-    t_last = t;
-  };
-  const uint32_t E = r->nb_entries;
-  const uint32_t T = r->nb_threads;
-  FILE* out = stdout;
-  if (stdout_path) {
-    out = fopen(stdout_path, "w");
-    if (!out) {
-      err = std::string("cannot open ") + stdout_path;
-      return NMG_ERR_IO;
-    }
-  }
-  auto close_out = [&]() {
-    if (out != stdout) fclose(out);
-    else fflush(out);
-  };
+// ---- the report: ma_finalize's steps, each a function over what they share
+namespace {
 
-  // ---- mem_sampling_finalize's messages (mem_sampling.c:321-344; none online, :313)
-  const bool online = opts && opts->online;
-  if (online && opts->dump_flags) {  // the reference's _dump_* read the NULL `samples` list online
-    close_out();
-    err = "dump modes are not available with online analysis (mem_sampling.c:644, 764, 799)";
-    return NMG_ERR_INVALID;
+// NMG_REPORT_TIMING=1: the time since the last mark, on stderr
+struct PhaseClock {
+  const bool on = getenv("NMG_REPORT_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void operator()(const char* name) {
+    if (!on) return;
+    const auto t = std::chrono::steady_clock::now();
+    fprintf(stderr, "nmg_report: %s %.3f s\n", name, std::chrono::duration<double>(t - last).count());
+    last = t;
   }
+};
+
+// the dump modes' files
+struct DumpFiles {
+  std::vector<File> site;  // by site index; callsite_dump_<id>.dat, opened at the site's first line
+  File all, unmatched;
+  bool maps_read = false;  // unmatched has its header
+};
+struct Report {
+  const nmg_host_results* r;
+  const nmg_object_meta* meta;
+  const nmg_report_options* opts;
+  const DumpInput* dump;
+  std::string& err;
+  FILE* out;  // stdout, or the file in its place
+  Registry reg;
+  bool online;
+  int dflags;
+  bool dump_single;
+  uint64_t nb_samples = 0, nb_found = 0;  // print_preamble's totals
+  OutDir dir;                             // made once the registry stands
+  DumpFiles dumps;
+};
+
+// mem_sampling_finalize's messages (mem_sampling.c:321-344; none online, :313) and the banner
+void print_preamble(Report& c, const uint64_t* found_override) {
+  const nmg_host_results* r = c.r;
   const int nbuf = (int)r->nb_buffers;
-  if (!online) fprintf(out, "Analyzing %d sample buffers\n", nbuf);
-  uint64_t so_far = 0, found_total = 0;
+  if (!c.online) fprintf(c.out, "Analyzing %d sample buffers\n", nbuf);
   size_t total_bytes = 0;
   for (int b = 0; b < nbuf; b++) {
-    if (b % 10 == 0 && !online)
-      fprintf(out, "\rAnalyzing sample buffer %d/%d. Total samples so far: %zu", b, nbuf, (size_t)so_far);
-    so_far += (uint64_t)(int64_t)(int32_t)r->buf_samples[b];  // int nb_samples (:325, :334, :934)
-    found_total += (uint64_t)(int64_t)(int32_t)r->buf_found[b];
+    if (b % 10 == 0 && !c.online)
+      fprintf(c.out, "\rAnalyzing sample buffer %d/%d. Total samples so far: %zu", b, nbuf, (size_t)c.nb_samples);
+    c.nb_samples += (uint64_t)(int64_t)(int32_t)r->buf_samples[b];  // int nb_samples (:325, :334, :934)
+    c.nb_found += (uint64_t)(int64_t)(int32_t)r->buf_found[b];
     total_bytes += r->buf_bytes[b];
   }
-  const uint64_t nb_samples_total = so_far;
-  if (found_override) found_total = *found_override;
-  if (!online) {
-    fprintf(out, "\n");
-    fprintf(out, "%zu bytes processed\n", total_bytes);
+  if (found_override) c.nb_found = *found_override;
+  if (!c.online) {
+    fprintf(c.out, "\n");
+    fprintf(c.out, "%zu bytes processed\n", total_bytes);
   }
-  fprintf(out, "---------------------------------\n");
-  fprintf(out, "         MEM ANALYZER\n");
-  fprintf(out, "---------------------------------\n");
+  fprintf(c.out, "---------------------------------\n");
+  fprintf(c.out, "         MEM ANALYZER\n");
+  fprintf(c.out, "---------------------------------\n");
+}
 
-  // ---- call sites
-  phase("buffers");
-  Registry reg(meta);
-  if (r->match_samples) {
-    const int rc = fill_registry(reg, r, meta, online, err, phase);
-    if (rc) {
-      close_out();
-      return rc;
-    }
-  }
-  std::vector<Site>& sites = reg.sites;
-  phase("call-site registry");
+// f, opened as `base` with its header line when it is not open yet; NULL: c.err
+FILE* opened(Report& c, File& f, const std::string& base, const char* header) {
+  if (!f && (f = c.dir.open(base, c.err))) fputs(header, f.get());
+  return f.get();
+}
 
-  // ---- dump modes (mem_sampling.c:895-914): per SAMPLE record in analysis order
-  const char* dir = opts && opts->output_dir ? opts->output_dir : ".";
-  const int dflags = opts ? opts->dump_flags : 0;
-  const bool dump_single = opts ? opts->dump_single_items != 0 : true;
-  mkdir(dir, S_IRWXU);  // get_log_dir (mem_intercept.c:402-409)
-  std::vector<FILE*> site_file(sites.size(), nullptr);
-  FILE* all_file = nullptr;
-  FILE* unmatched_file = nullptr;
-  auto open_out = [&](const std::string& base) -> FILE* {
-    FILE* f = fopen((std::string(dir) + "/" + base).c_str(), "w");
-    if (!f) err = "cannot open " + std::string(dir) + "/" + base;
-    return f;
-  };
-  auto close_dumps = [&]() {
-    for (FILE*& f : site_file)
-      if (f) fclose(f), f = nullptr;
-    if (all_file) fclose(all_file), all_file = nullptr;
-    if (unmatched_file) fclose(unmatched_file), unmatched_file = nullptr;
-  };
-  if (dflags & NMG_DUMP_UNMATCHED) {  // opened at init (mem_intercept.c:528-535)
-    unmatched_file = open_out("unmatched_samples.log");
-    if (!unmatched_file) {
-      close_out();
-      return NMG_ERR_IO;
-    }
+// One SAMPLE record's lines in the dump files.  false: a file could not be opened.
+bool dump_sample(Report& c, const DumpBuffer& b, uint64_t cur) {
+  const uint64_t ts = load<uint64_t>(b.data + cur + 8), addr = load<uint64_t>(b.data + cur + 16);
+  const uint64_t w = load<uint64_t>(b.data + cur + 24);
+  const std::string level = data_src_level(load<uint64_t>(b.data + cur + 32));
+  const char acc = b.access == NMG_ACCESS_READ ? 'r' : 'w';
+  const uint32_t m = b.match[cur / 8];
+  if (!m) {
+    if (!c.dumps.maps_read) write_maps_header(c.dumps.unmatched.get(), c.opts);
+    c.dumps.maps_read = true;
+    fprintf(c.dumps.unmatched.get(), "%u %" PRIu64 " 0x%" PRIxPTR " %s %" PRIu64 " %c\n", b.thread_rank, ts,
+            (uintptr_t)addr, level.c_str(), w, acc);
+    return true;
   }
-  if (dump && r->match_samples) {
-    bool maps_read = false;
-    const bool dump_matched = dflags & (NMG_DUMP_CALLSITES | NMG_DUMP_ALL);
-    for (const DumpBuffer& b : dump->buffers) {
-      const char acc = b.access == NMG_ACCESS_READ ? 'r' : 'w';
-      for (uint64_t cur = 0; cur + 8 <= b.len;) {
-        const uint32_t type = load<uint32_t>(b.data + cur);
-        const uint16_t size = load<uint16_t>(b.data + cur + 6);
-        if (size == 0) break;  // (the analysis already reported it)
-        if (type == 9 && cur + 40 <= b.len) {
-          const uint64_t ts = load<uint64_t>(b.data + cur + 8), addr = load<uint64_t>(b.data + cur + 16);
-          const uint64_t w = load<uint64_t>(b.data + cur + 24), dsrc = load<uint64_t>(b.data + cur + 32);
-          const uint32_t m = b.match[cur / 8];
-          if (!m) {
-            if (unmatched_file) {
-              if (!maps_read) {
-                write_maps_header(unmatched_file, opts);
-                maps_read = true;
-              }
-              fprintf(unmatched_file, "%u %" PRIu64 " 0x%" PRIxPTR " %s %" PRIu64 " %c\n", b.thread_rank, ts,
-                      (uintptr_t)addr, data_src_level(dsrc).c_str(), w, acc);
-            }
-          } else if (dump_matched) {
-            const uint32_t e = m - 1;
-            const uint64_t offset = addr - dump->entry_addr[e];
-            if ((dflags & NMG_DUMP_ALL) && meta[e].mem_type != kMemTypeStack) {  // _dump_mem_info (:740-773)
-              if (!all_file) {
-                if (!(all_file = open_out("all_memory_accesses.dat"))) break;
-                fprintf(all_file, "#thread_rank timestamp object_id offset mem_level access_weight access_type\n");
-              }
-              fprintf(all_file, "%u %" PRIu64 " %u %" PRIu64 " %s %" PRIu64 " %c\n", b.thread_rank, ts, meta[e].id,
-                      offset, data_src_level(dsrc).c_str(), w, acc);
-            }
-            if (dump_single && meta[e].mem_type != kMemTypeStack) {  // _dump_call_site (:775-808)
-              const int64_t si = reg.find(e);
-              if (si >= 0) {
-                if (!site_file[si]) {
-                  char fn[64];
-                  snprintf(fn, sizeof(fn), "callsite_dump_%d.dat", (int)sites[si].id);
-                  if (!(site_file[si] = open_out(fn))) break;
-                  fprintf(site_file[si], "#thread_rank timestamp offset mem_level access_weight access_type\n");
-                }
-                fprintf(site_file[si], "%u %" PRIu64 " %" PRIuPTR " %s %" PRIu64 " %c\n", b.thread_rank, ts,
-                        (uintptr_t)offset, data_src_level(dsrc).c_str(), w, acc);
-              }
-            }
-          }
-        }
-        cur += size;
-      }
-      if (!err.empty()) {
-        close_dumps();
-        close_out();
+  const uint32_t e = m - 1;
+  const uint64_t offset = addr - c.dump->entry_addr[e];
+  if (c.meta[e].mem_type == kMemTypeStack) return true;
+  if (c.dflags & NMG_DUMP_ALL) {  // _dump_mem_info (:740-773)
+    FILE* f = opened(c, c.dumps.all, "all_memory_accesses.dat",
+                     "#thread_rank timestamp object_id offset mem_level access_weight access_type\n");
+    if (!f) return false;
+    fprintf(f, "%u %" PRIu64 " %u %" PRIu64 " %s %" PRIu64 " %c\n", b.thread_rank, ts, c.meta[e].id, offset,
+            level.c_str(), w, acc);
+  }
+  const int64_t si = c.dump_single ? c.reg.find(e) : -1;  // _dump_call_site (:775-808)
+  if (si < 0) return true;
+  FILE* f = opened(c, c.dumps.site[si], site_file("dump", c.reg.sites[si].id),
+                   "#thread_rank timestamp offset mem_level access_weight access_type\n");
+  if (!f) return false;
+  fprintf(f, "%u %" PRIu64 " %" PRIuPTR " %s %" PRIu64 " %c\n", b.thread_rank, ts, (uintptr_t)offset, level.c_str(), w,
+          acc);
+  return true;
+}
+
+// The dump modes (mem_sampling.c:895-914): per SAMPLE record in analysis order
+int dump_records(Report& c) {
+  if (c.dflags & NMG_DUMP_UNMATCHED)  // opened at init (mem_intercept.c:528-535)
+    if (!(c.dumps.unmatched = c.dir.open("unmatched_samples.log", c.err))) return NMG_ERR_IO;
+  if (!c.dump || !c.r->match_samples) return NMG_OK;
+  c.dumps.site.resize(c.reg.sites.size());
+  const bool matched = c.dflags & (NMG_DUMP_CALLSITES | NMG_DUMP_ALL), unmatched = c.dumps.unmatched != nullptr;
+  for (const DumpBuffer& b : c.dump->buffers)
+    for (uint64_t cur = 0; cur + 8 <= b.len;) {
+      const uint32_t type = load<uint32_t>(b.data + cur);
+      const uint16_t size = load<uint16_t>(b.data + cur + 6);
+      if (size == 0) break;  // (the analysis already reported it)
+      if (type == 9 && cur + 40 <= b.len && (b.match[cur / 8] ? matched : unmatched) && !dump_sample(c, b, cur))
         return NMG_ERR_IO;
+      cur += size;
+    }
+  return NMG_OK;
+}
+
+// __print_call_site_stats (:1489-1503): the cumulated counters of a site's
+// objects, whose min / max stay 0 (memset, and ACC_COUNTER's inverted tests: Q8)
+void site_counters(const Report& c, const Site& site, nmg_mem_counters cc[2]) {
+  memset(cc, 0, 2 * sizeof(cc[0]));
+  for (uint32_t e : site.objects)
+    for (uint32_t a = 0; a < 2; a++) {
+      const uint64_t* cw = c.r->count_weight + (uint64_t)e * 4 + a * 2;
+      const uint64_t* lv = c.dump->levels + ((uint64_t)e * 2 + a) * kLevelWords;
+      cc[a].total_count += cw[0];
+      cc[a].total_weight += cw[1];
+      cc[a].na_miss_count += lv[0];
+      for (uint32_t k = 0; k < kBuckets; k++) {
+        cc[a].b[k].count += lv[1 + 2 * k];
+        cc[a].b[k].sum_weight += lv[2 + 2 * k];
       }
     }
-  }
+}
 
-  // ---- ma_finalize prints (mem_analyzer.c:1877-1881)
-  phase("dumps");
-  print_counters(out, r->global);
-  fprintf(out, "Summary of the call sites:\n");
-  fprintf(out, "--------------------------\n");
-  fprintf(out, "Sorting call sites\n");
-  std::vector<int64_t> order = sort_sites(sites);
-  phase("sort");
-  // __remove_site during the sort (mem_analyzer.c:1506-1528): the site the
-  // walk stops at -- the removed one when it heads the list, else its
-  // predecessor (quirk Q10) -- gets callsite_summary_<id>.dat and its dump
-  // file closed, if it has one.  The list is id-descending; removals run in
-  // the reverse of the final order.
-  if (dump) {
-    std::set<int64_t> remaining;
-    for (int64_t i = 0; i < (int64_t)sites.size(); i++) remaining.insert(i);
-    for (auto it = order.rbegin(); it != order.rend(); ++it) {
-      auto pos = remaining.find(*it);
-      auto nxt = std::next(pos);
-      const int64_t cur = nxt == remaining.end() ? *it : *nxt;
-      remaining.erase(pos);
-      if (!site_file[cur]) continue;
-      // __print_call_site_stats (:1489-1503): the cumulated counters, whose
-      // min / max stay 0 (memset, and ACC_COUNTER's inverted tests: Q8)
-      nmg_mem_counters cc[2];
-      memset(cc, 0, sizeof(cc));
-      for (uint32_t e : sites[cur].objects)
-        for (uint32_t a = 0; a < 2; a++) {
-          const uint64_t* cw = r->count_weight + (uint64_t)e * 4 + a * 2;
-          const uint64_t* lv = dump->levels + ((uint64_t)e * 2 + a) * kLevelWords;
-          cc[a].total_count += cw[0];
-          cc[a].total_weight += cw[1];
-          cc[a].na_miss_count += lv[0];
-          for (uint32_t k = 0; k < kBuckets; k++) {
-            cc[a].b[k].count += lv[1 + 2 * k];
-            cc[a].b[k].sum_weight += lv[2 + 2 * k];
-          }
-        }
-      char fn[64];
-      snprintf(fn, sizeof(fn), "callsite_summary_%d.dat", (int)sites[cur].id);
-      FILE* sf = open_out(fn);
-      if (!sf) {
-        close_dumps();
-        close_out();
-        return NMG_ERR_IO;
-      }
-      print_counters(sf, cc);
-      fclose(sf);
-      fclose(site_file[cur]);
-      site_file[cur] = nullptr;
-    }
+// __remove_site during the sort (mem_analyzer.c:1506-1528): the site the walk
+// stops at -- the removed one when it heads the list, else its predecessor
+// (quirk Q10) -- gets callsite_summary_<id>.dat and its dump file closed, if it
+// has one.  The list is id-descending; removals run in the reverse of the
+// final order.
+int write_summaries(Report& c, const std::vector<int64_t>& order) {
+  if (c.dumps.site.empty()) return NMG_OK;  // (no dump file was ever open)
+  std::set<int64_t> remaining;
+  for (int64_t i = 0; i < (int64_t)c.reg.sites.size(); i++) remaining.insert(i);
+  for (auto it = order.rbegin(); it != order.rend(); ++it) {
+    auto pos = remaining.find(*it);
+    auto nxt = std::next(pos);
+    const int64_t cur = nxt == remaining.end() ? *it : *nxt;
+    remaining.erase(pos);
+    if (!c.dumps.site[cur]) continue;
+    nmg_mem_counters cc[2];
+    site_counters(c, c.reg.sites[cur], cc);
+    const File sf = c.dir.open(site_file("summary", c.reg.sites[cur].id), c.err);
+    if (!sf) return NMG_ERR_IO;
+    print_counters(sf.get(), cc);
+    c.dumps.site[cur].reset();
   }
-  close_dumps();  // the rest stay open until exit in the reference
-  std::string cs_path = std::string(dir) + "/call_sites.log";
-  FILE* cf = fopen(cs_path.c_str(), "w");
-  if (!cf) {
-    close_out();
-    err = "cannot open " + cs_path;
-    return NMG_ERR_IO;
-  }
-  // per-entry ranges of the (entry, thread, page, count) rows
-  std::vector<int64_t> cell_begin;
-  auto index_cells = [&]() {
-    if (!cell_begin.empty()) return;
-    cell_begin.assign((size_t)E + 1, 0);
-    for (int64_t i = 0; i < r->nb_cells; i++) cell_begin[r->cells[4 * i] + 1]++;
-    for (uint32_t e = 0; e < E; e++) cell_begin[e + 1] += cell_begin[e];
-  };
+  return NMG_OK;
+}
 
+// __plot_counters (mem_analyzer.c:1557-1585): one callsite_counters_<id>.dat
+// per site of `jobs`.  The files are independent: written by a pool of host
+// threads (NMG_REPORT_THREADS, default min(16, cores)); the first error stops
+// the pool.
+int write_site_counters(Report& c, const std::vector<int64_t>& jobs) {
+  const nmg_host_results* r = c.r;
+  const std::vector<int64_t> cell_begin = entry_ranges(r->cells, r->nb_cells, r->nb_entries);
+  unsigned nth = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  if (const char* e = getenv("NMG_REPORT_THREADS")) nth = (unsigned)std::max(1, atoi(e));
+  nth = (unsigned)std::min<size_t>(nth, jobs.size());
   int rc = NMG_OK;
+  std::atomic<size_t> next{0};
+  std::mutex mu;
+  auto work = [&]() {
+    for (size_t j; (j = next.fetch_add(1)) < jobs.size();) {
+      const Site& s = c.reg.sites[jobs[j]];
+      SiteHist sh(SiteShape(s, r->nb_threads));
+      for (uint32_t e : s.objects)
+        for (int64_t i = cell_begin[e]; i < cell_begin[e + 1]; i++) {
+          const uint32_t* q = r->cells + 4 * i;
+          sh.add(q[2], q[1], q[3]);
+        }
+      std::string why;
+      const File df = c.dir.open(site_file("counters", s.id), why);
+      if (!df) {
+        std::lock_guard<std::mutex> g(mu);
+        if (rc == NMG_OK) rc = NMG_ERR_IO, c.err = why;
+        next = jobs.size();  // stop the pool
+        break;
+      }
+      write_matrix(df.get(), sh, [&](char* buf, size_t size, uint64_t pg, uint32_t th) {
+        return snprintf(buf, size, "\t%d", (int)sh.get(pg, th));
+      });
+    }
+  };
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < nth; t++) pool.emplace_back(work);
+  work();
+  for (std::thread& t : pool) t.join();
+  return rc;
+}
+
+// print_call_site_summary (:1597-1640) of the sites with samples, in report
+// order, on stdout and in call_sites.log; then their page files
+int list_sites(Report& c, FILE* cf, const std::vector<int64_t>& order) {
   std::vector<int64_t> jobs;  // sites whose page file is written (in report order)
   for (int64_t idx : order) {
-    const Site& s = sites[idx];
+    const Site& s = c.reg.sites[idx];
     if (!(s.read_count || s.write_count)) continue;
     double avg = 0;
     if (s.read_count) avg = (double)s.read_weight / s.read_count;
     for (int k = 0; k < 2; k++)
-      fprintf(k ? out : cf,
+      fprintf(k ? c.out : cf,
               "%d\t%s (size=%zu) - %d buffers. %zu read access (total weight: %" PRIu64
               ", avg weight: %f). %" PRIu64 " wr_access\n",
               (int)s.id, s.caller.c_str(), (size_t)s.buffer_size, (int)s.nb_mallocs, (size_t)s.read_count,
               s.read_weight, avg, s.write_count);
-    if (dump_single && s.mem_type != kMemTypeStack) jobs.push_back(idx);
+    if (c.dump_single && s.mem_type != kMemTypeStack) jobs.push_back(idx);
   }
-  if (!jobs.empty()) {
-    // __plot_counters (mem_analyzer.c:1557-1585): one callsite_counters_<id>.dat
-    // per site, (buffer_size / 4096 + 1) rows x next_thread_rank columns.  The
-    // files are independent: written by a pool of host threads
-    // (NMG_REPORT_THREADS, default min(16, cores)).
-    index_cells();
-    unsigned nth = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char* e = getenv("NMG_REPORT_THREADS")) nth = (unsigned)std::max(1, atoi(e));
-    nth = (unsigned)std::min<size_t>(nth, jobs.size());
-    std::atomic<size_t> next{0};
-    std::mutex mu;
-    auto work = [&]() {
-      std::string line;
-      char cell[16];
-      for (size_t j; (j = next.fetch_add(1)) < jobs.size();) {
-        const Site& s = sites[jobs[j]];
-        SiteHist sh;
-        const uint64_t rows = s.mem_info_buffer_size / kPageSize + 1;
-        sh.init(rows, T);
-        for (uint32_t e : s.objects)
-          for (int64_t i = cell_begin[e]; i < cell_begin[e + 1]; i++) {
-            const uint32_t* c = r->cells + 4 * i;
-            sh.add(c[2], c[1], c[3]);
-          }
-        char fn[4096];
-        snprintf(fn, sizeof(fn), "%s/callsite_counters_%d.dat", dir, (int)s.id);
-        FILE* df = fopen(fn, "w");
-        if (!df) {
-          std::lock_guard<std::mutex> g(mu);
-          if (rc == NMG_OK) {
-            rc = NMG_ERR_IO;
-            err = std::string("cannot open ") + fn;
-          }
-          next = jobs.size();  // stop the pool
-          break;
-        }
-        for (uint64_t i = 0; i < rows; i++) {
-          line.clear();
-          for (uint32_t th = 0; th < T; th++) {
-            int n = snprintf(cell, sizeof(cell), "\t%d", (int)sh.get(i, th));
-            line.append(cell, n);
-          }
-          line.push_back('\n');
-          fwrite(line.data(), 1, line.size(), df);
-        }
-        fclose(df);
-      }
-    };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nth; t++) pool.emplace_back(work);
-    work();
-    for (std::thread& t : pool) t.join();
+  return jobs.empty() ? NMG_OK : write_site_counters(c, jobs);
+}
+
+}  // namespace
+
+int write_report(const nmg_host_results* r, const nmg_object_meta* meta, const nmg_report_options* opts,
+                 const char* stdout_path, std::string& err, const DumpInput* dump, const uint64_t* found_override) {
+  PhaseClock phase;
+  const File out(stdout_path ? fopen(stdout_path, "w") : stdout);
+  if (!out) {
+    err = std::string("cannot open ") + stdout_path;
+    return NMG_ERR_IO;
   }
-  fclose(cf);
+  Report c{r, meta, opts, dump, err, out.get(), Registry(meta), opts && opts->online, opts ? opts->dump_flags : 0,
+           opts ? opts->dump_single_items != 0 : true};
+  if (c.online && c.dflags) {  // the reference's _dump_* read the NULL `samples` list online
+    err = "dump modes are not available with online analysis (mem_sampling.c:644, 764, 799)";
+    return NMG_ERR_INVALID;
+  }
+  print_preamble(c, found_override);
+  phase("buffers");
+  if (const int rc = site_registry(c.reg, r, c.online, err, std::ref(phase))) return rc;
+  phase("call-site registry");
+  c.dir = OutDir(opts);
+  if (const int rc = dump_records(c)) return rc;
+  phase("dumps");
+  // ma_finalize prints (mem_analyzer.c:1877-1881)
+  print_counters(c.out, r->global);
+  fprintf(c.out, "Summary of the call sites:\n");
+  fprintf(c.out, "--------------------------\n");
+  fprintf(c.out, "Sorting call sites\n");
+  const std::vector<int64_t> order = sort_sites(c.reg.sites);
+  phase("sort");
+  if (const int rc = write_summaries(c, order)) return rc;
+  c.dumps = DumpFiles();  // (the rest stay open until exit in the reference)
+  File cf = c.dir.open("call_sites.log", err);
+  if (!cf) return NMG_ERR_IO;
+  int rc = list_sites(c, cf.get(), order);
+  cf.reset();
   phase("call_sites.log + page files");
-  if (!rc && (dflags & NMG_DUMP_ALL)) {
-    if (r->objects)
-      rc = write_object_summary(std::string(dir) + "/all_memory_objects.dat", r, meta, opts, err);
-    else {
+  if (!rc && (c.dflags & NMG_DUMP_ALL)) {
+    if (r->objects) {
+      rc = write_object_summary(c.dir, r, meta, opts, err);
+    } else {
       rc = NMG_ERR_INVALID;
       err = "NMG_DUMP_ALL needs nmg_host_results.objects (all_memory_objects.dat)";
     }
   }
-  if (rc) {
-    close_out();
-    return rc;
-  }
+  if (rc) return rc;
   // mem_sampling_statistics (mem_sampling.c:357-361): a float percentage
-  float percent = 100.0 * (nb_samples_total - found_total) / nb_samples_total;
-  fprintf(out, "%" PRIu64 " samples (including %" PRIu64 " samples that do not match a known memory buffer / %f%%)\n",
-          nb_samples_total, nb_samples_total - found_total, percent);
-  close_out();
+  float percent = 100.0 * (c.nb_samples - c.nb_found) / c.nb_samples;
+  fprintf(c.out, "%" PRIu64 " samples (including %" PRIu64 " samples that do not match a known memory buffer / %f%%)\n",
+          c.nb_samples, c.nb_samples - c.nb_found, percent);
   return NMG_OK;
 }
 
 }  // namespace nmg
 
-extern "C" int nmg_report_timeline_host(const nmg_host_results* res, const nmg_object_meta* meta,
-                                        const nmg_report_options* opts, const nmg_timeline_options* tl,
-                                        const uint32_t* rows, int64_t n) {
-  if (!res || !tl || n < 0 || (n && !rows) ||
-      (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight || !res->buffer_size)) ||
-      res->nb_threads > NMG_MAX_THREADS || tl->bin_shift > 63 || tl->nb_bins < 1 || tl->nb_bins > 4096 ||
-      tl->row_shift > 20 || tl->reserved != 0)
-    return NMG_ERR_INVALID;
-  for (int64_t i = 0; i < n; i++)
-    if (rows[5 * i] >= res->nb_entries || rows[5 * i + 1] >= tl->nb_bins || rows[5 * i + 2] >= res->nb_threads)
-      return NMG_ERR_INVALID;
-  std::string err;
-  int rc = nmg::write_timeline(res, meta, opts, tl, rows, n, err);
-  if (rc && !err.empty()) fprintf(stderr, "nmg_report_timeline: %s\n", err.c_str());
-  return rc;
-}
-
-extern "C" int nmg_report_page_cost_host(const nmg_host_results* res, const nmg_object_meta* meta,
-                                         const nmg_report_options* opts, const uint64_t* rows, int64_t n) {
-  if (!res || n < 0 || (n && !rows) ||
-      (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight || !res->buffer_size)) ||
-      res->nb_threads > NMG_MAX_THREADS)
-    return NMG_ERR_INVALID;
-  for (int64_t i = 0; i < n; i++)
-    if (rows[4 * i] >= res->nb_entries || rows[4 * i + 1] >= res->nb_threads) return NMG_ERR_INVALID;
-  std::string err;
-  int rc = nmg::write_page_cost(res, meta, opts, rows, n, err);
-  if (rc && !err.empty()) fprintf(stderr, "nmg_report_page_cost: %s\n", err.c_str());
-  return rc;
-}
-
+// ---- the host entry points: their arguments checked, the writer's text on stderr
 namespace {
+
+// res, its thread count, and what the site registry reads per entry
+bool registry_args(const nmg_host_results* res, const nmg_object_meta* meta) {
+  return res && res->nb_threads <= NMG_MAX_THREADS &&
+         (!res->nb_entries || (meta && res->first_ordinal && res->count_weight && res->buffer_size));
+}
+
+// res->cells: there, every entry in range, sorted by entry
+bool cells_args(const nmg_host_results* res) {
+  if (res->nb_cells && !res->cells) return false;
+  for (int64_t i = 0; i < res->nb_cells; i++)
+    if (res->cells[4 * i] >= res->nb_entries || (i && res->cells[4 * i] < res->cells[4 * i - 4])) return false;
+  return true;
+}
+
+int said(const char* who, int rc, const std::string& err) {
+  if (rc && !err.empty()) fprintf(stderr, "%s: %s\n", who, err.c_str());
+  return rc;
+}
+
 // the host's view of the page cells: an entry's pages, and whether the engine
 // keeps them dense (CellCursor::place's per-entry cap; budgets aside).  With
 // NMG_PLACE_HUGE the cap only chooses how a group is walked: every entry of
 // res->cells contributes.
 bool placement_host_args(const nmg_host_results* res, const nmg_placement_options* p, nmg::PlaceMap& map,
                          std::vector<uint64_t>& npages, std::vector<uint8_t>& dense) {
-  if (!res || (res->nb_entries && !res->buffer_size) || (res->nb_cells && !res->cells) || res->nb_cells < 0 ||
-      res->nb_threads > NMG_MAX_THREADS || nmg::placement_map(p, res->nb_threads, map) ||
-      (p->source & ~(uint64_t)NMG_PLACE_HUGE) != NMG_PLACE_PAGE_COUNTS)  // (nmg_host_results has no cost rows)
+  if (!res || (res->nb_entries && !res->buffer_size) || res->nb_cells < 0 || res->nb_threads > NMG_MAX_THREADS ||
+      nmg::placement_map(p, res->nb_threads, map) ||
+      (p->source & ~(uint64_t)NMG_PLACE_HUGE) != NMG_PLACE_PAGE_COUNTS ||  // (nmg_host_results has no cost rows)
+      !cells_args(res))
     return false;
-  for (int64_t i = 0; i < res->nb_cells; i++)
-    if (res->cells[4 * i] >= res->nb_entries || (i && res->cells[4 * i] < res->cells[4 * i - 4])) return false;
   npages.resize(res->nb_entries);
   dense.resize(res->nb_entries);
   for (uint32_t e = 0; e < res->nb_entries; e++) {
@@ -1137,16 +1107,37 @@ bool placement_host_args(const nmg_host_results* res, const nmg_placement_option
   }
   return true;
 }
+
 }  // namespace
+
+extern "C" int nmg_report_timeline_host(const nmg_host_results* res, const nmg_object_meta* meta,
+                                        const nmg_report_options* opts, const nmg_timeline_options* tl,
+                                        const uint32_t* rows, int64_t n) {
+  if (!registry_args(res, meta) || !tl || n < 0 || (n && !rows) || tl->bin_shift > 63 || tl->nb_bins < 1 ||
+      tl->nb_bins > 4096 || tl->row_shift > 20 || tl->reserved != 0)
+    return NMG_ERR_INVALID;
+  for (int64_t i = 0; i < n; i++)
+    if (rows[5 * i] >= res->nb_entries || rows[5 * i + 1] >= tl->nb_bins || rows[5 * i + 2] >= res->nb_threads)
+      return NMG_ERR_INVALID;
+  std::string err;
+  return said("nmg_report_timeline", nmg::write_timeline(res, meta, opts, tl, rows, n, err), err);
+}
+
+extern "C" int nmg_report_page_cost_host(const nmg_host_results* res, const nmg_object_meta* meta,
+                                         const nmg_report_options* opts, const uint64_t* rows, int64_t n) {
+  if (!registry_args(res, meta) || n < 0 || (n && !rows)) return NMG_ERR_INVALID;
+  for (int64_t i = 0; i < n; i++)
+    if (rows[4 * i] >= res->nb_entries || rows[4 * i + 1] >= res->nb_threads) return NMG_ERR_INVALID;
+  std::string err;
+  return said("nmg_report_page_cost", nmg::write_page_cost(res, meta, opts, rows, n, err), err);
+}
 
 extern "C" int nmg_report_placement_host(const nmg_host_results* res, const nmg_object_meta* meta,
                                          const nmg_report_options* opts, const nmg_placement_options* p) {
   nmg::PlaceMap map;
   std::vector<uint64_t> npages;
   std::vector<uint8_t> dense;
-  if (!placement_host_args(res, p, map, npages, dense) ||
-      (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight)))
-    return NMG_ERR_INVALID;
+  if (!placement_host_args(res, p, map, npages, dense) || !registry_args(res, meta)) return NMG_ERR_INVALID;
   std::string err;
   nmg::PlaceGroups g;
   std::vector<nmg::PlaceSite> sites;
@@ -1157,8 +1148,7 @@ extern "C" int nmg_report_placement_host(const nmg_host_results* res, const nmg_
     nmg::placement_blocks_host(g, map, res->cells, res->nb_cells, res->nb_entries, rows);
     rc = nmg::write_blocks(sites, rows.data(), (int64_t)(rows.size() / 5), opts, err);
   }
-  if (rc && !err.empty()) fprintf(stderr, "nmg_report_placement: %s\n", err.c_str());
-  return rc;
+  return said("nmg_report_placement", rc, err);
 }
 
 // Internal (not in include/numamma_gpu.h; tools/placement_timing.py and the
@@ -1182,15 +1172,10 @@ extern "C" int64_t nmg_debug_object_blocks_host(const nmg_host_results* res, con
 
 extern "C" int nmg_report_host(const nmg_host_results* res, const nmg_object_meta* meta,
                                const nmg_report_options* opts, const char* stdout_path) {
-  if (!res || (res->nb_entries && (!meta || !res->first_ordinal || !res->count_weight || !res->buffer_size)) ||
-      (res->nb_buffers && (!res->buf_samples || !res->buf_found || !res->buf_bytes)) ||
-      (res->nb_cells && !res->cells) || res->nb_threads > NMG_MAX_THREADS)
+  if (!registry_args(res, meta) || (res->nb_buffers && (!res->buf_samples || !res->buf_found || !res->buf_bytes)) ||
+      !cells_args(res))
     return NMG_ERR_INVALID;
-  for (int64_t i = 0; i < res->nb_cells; i++)
-    if (res->cells[4 * i] >= res->nb_entries || (i && res->cells[4 * i] < res->cells[4 * i - 4]))
-      return NMG_ERR_INVALID;
   std::string err;
-  int rc = nmg::write_report(res, meta, opts, stdout_path, err);
-  if (rc && !err.empty()) fprintf(stderr, "nmg_report: %s\n", err.c_str());
-  return rc;
+  return said("nmg_report", nmg::write_report(res, meta, opts, stdout_path, err), err);
 }
+
