@@ -128,6 +128,9 @@ struct LookupSet {
 struct RouteTable {
   bool ok = false;  // partitions built for the current table
   uint32_t nparts = 0;
+  RSeg rsegs[kRouteSegs] = {};  // the route pass's directory segments
+  uint32_t nrsegs = 0;
+  uint64_t tbase = 0;  // compact records: timestamps relative to this (XLayout)
   DevBuf<PartInfo> d_parts;
   DevBuf<uint64_t> d_pbounds;  // [kMaxParts + 1] partition starts, ascending
   DevBuf<uint16_t> d_pdir;     // [kRouteDir] the route pass's directory over them
@@ -165,62 +168,6 @@ struct RoutePool {
   DevBuf<uint32_t> d_ctl;     // [3] items, dequeue head, overflow records
   DevBuf<uint4> d_ovf16;      // overflow list (route pass, pool exhausted)
   DevBuf<unsigned long long> d_ovfx;
-};
-
-// The host's entry table: per entry id, the object as the latest table lists
-// it and the page cells it counts into.  The arrays are contiguous (the report
-// and the uploads read their data()).
-struct EntryTable {
-  std::vector<uint64_t> hist_base;  // first dense cell, kHistSparse if sparse / none
-  std::vector<uint64_t> npages;     // buffer_size / kPageSize + 1 of the cells it has
-  std::vector<uint64_t> buffer_size, entry_addr;
-  std::vector<nmg_object> objects;    // the report's objects
-  std::vector<DevEntry> dev_entries;  // host copy of d_entries (cells and id; nmg_set_objects' table also its objects)
-  std::vector<uint32_t> sparse_entries;  // sparse idx -> entry
-  CellCursor cur;  // cur.cells: dense cells per thread (padded between calls)
-
-  uint64_t cells() const { return cur.cells; }
-  // E entries; new ones are objects not described yet: one page, no cells
-  void resize(uint32_t E) {
-    const size_t E0 = dev_entries.size();
-    hist_base.resize(E, kHistSparse);
-    npages.resize(E, 1);
-    buffer_size.resize(E, 0);
-    entry_addr.resize(E, 0);
-    objects.resize(E, nmg_object{0, 0, 0, 0});
-    dev_entries.resize(E, DevEntry{0, 0, 0, 0, kHistSparse, ~0u, 0, 0, 0, 0});
-    for (size_t e = E0; e < E; e++) dev_entries[e].id = (uint32_t)e;
-  }
-  // what resize and place added since the table had E entries and cursor c, dropped again
-  void truncate(uint32_t E, const CellCursor& c) {
-    resize(E);
-    sparse_entries.resize(c.nsparse);
-    cur = c;
-  }
-  // entry id as object o describes it (the report's view)
-  void describe(uint32_t id, const nmg_object& o) {
-    objects[id] = o;
-    buffer_size[id] = o.buffer_size;
-    entry_addr[id] = o.buffer_addr;
-  }
-  // the device record of entry id (its cells) as object o describes it
-  DevEntry dev_entry(uint32_t id, const nmg_object& o) const {
-    DevEntry d = dev_entries[id];
-    d.addr = o.buffer_addr;
-    d.end = o.buffer_addr + o.buffer_size;
-    d.alloc = o.alloc_date;
-    d.free = o.free_date;
-    return d;
-  }
-  // page cells for np pages of entry id (CellCursor::place); the entry is unchanged unless placed
-  Placement place(uint32_t id, uint64_t np, bool must_be_dense) {
-    DevEntry& d = dev_entries[id];
-    uint64_t base = kHistSparse;
-    const Placement how = cur.place(np, must_be_dense, &base, &d.sidx);
-    if (how == kPlaceDense) d.hist = hist_base[id] = base;
-    if (how == kPlaceSparse) sparse_entries.push_back(id);
-    return how;
-  }
 };
 
 // The sparse table's used slots compacted on the device: n interleaved (key,
@@ -509,9 +456,6 @@ struct nmg_engine {
   // the current table, and the per-analysis chunk pool
   RouteTable rt;
   uint64_t route_launches = 0;    // analyses (or streamed chunks) that took the partition-first path
-  RSeg rsegs[kRouteSegs];         // the route pass's directory segments
-  uint64_t route_tbase = 0;       // compact records: timestamps relative to this (XLayout)
-  uint32_t nrsegs = 0;
   RoutePool rpool;
   bool sched_route = false;       // d_sdescs / d_ranges hold the analysis-order schedule
   uint32_t route_sched_key = 0;   // what the pools were laid out for (route_key)
@@ -586,7 +530,6 @@ int check_table(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, 
                        uint32_t n);
 int build_lookup(nmg_engine* h, LookupSet& l, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
                  const std::vector<DevEntry>& chain, DevEntry* chain_dev);
-void route_segments(const uint64_t* b, uint32_t P, RSeg* seg, uint32_t* nseg, std::vector<uint16_t>& dir);
 int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t K,
                             const std::vector<DevEntry>& dev, const uint32_t* ids);
 int grow_entries(nmg_engine* h, uint32_t newE, const uint32_t* ids, const nmg_object* objs, uint32_t n);

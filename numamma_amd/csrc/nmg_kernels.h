@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "nmg_internal.h"
+#include "nmg_table_build.h"
 
 namespace nmg {
 
@@ -15,12 +16,6 @@ constexpr int kWG = 1024;                      // one workgroup per CU
 constexpr uint32_t kSampleType = 9;            // PERF_RECORD_SAMPLE
 constexpr uint32_t kRecBytes = 40;             // perf_event_header (8) + struct mem_sample (32)
 constexpr uint32_t kWinBytes = kWG * kRecBytes;  // one 40 B stride slot per lane per window
-constexpr uint32_t kLdsNodes = 1023;           // keys held in LDS with their node records (<= 10 levels)
-// Larger tables: up to 4095 fences (every S-th key) in a 12-level Eytzinger
-// tree in LDS, then one load from a per-fence-bucket directory in global memory
-constexpr uint32_t kFenceLevels = 12;
-constexpr uint32_t kMaxFences = (1u << kFenceLevels) - 1;
-constexpr uint32_t kShiftSearch = 0xff;        // bucket without a directory: binary search of its keys
 // One LDS region holds the lookup structure of either mode:
 //   <= kLdsNodes keys: Eytzinger keys (8 KiB) | node records (32 KiB) | node info (8 KiB)
 //   larger tables:     Eytzinger fences (32 KiB) | per-bucket directory shift (4 KiB)
@@ -62,7 +57,6 @@ constexpr bool kPackObj = true;
 constexpr uint32_t kPackShift = 44;  // kModeDenseObj: per-entry count << 44 | weight sum
 static_assert((uint64_t)kDensePageWindows * kWG < (1ull << (64 - kPackShift)), "packed count");
 static_assert(kDensePageWindows * kWG < 65536u, "u16 page counts");
-constexpr uint32_t kEmpty32 = 0xffffffffu;
 constexpr uint64_t kEmpty64 = ~0ull;
 // internal ablation switches (tools/ablate.py only; not part of the C-ABI)
 constexpr uint32_t kDbgLoadOnly = 0x100;   // stage + validate windows, decode nothing
@@ -91,23 +85,6 @@ struct BufDesc {
   uint64_t seq;  // analysis-order index (global across shards)
 };
 static_assert(sizeof(BufDesc) == 32, "BufDesc");
-
-// One table entry (64 B).  The node array holds, for node k, a copy of its
-// newest entry with `first` = its entry id and `count` = the node's number of
-// entries, so the common one-entry node costs a single dependent load.
-struct DevEntry {
-  uint64_t addr;   // buffer_addr
-  uint64_t end;    // buffer_addr + buffer_size (mod 2^64, as the reference's void* sum)
-  uint64_t alloc;  // alloc_date
-  uint64_t free;   // free_date
-  uint64_t hist;   // dense histogram base cell, or kHistSparse
-  uint32_t sidx;   // sparse index (valid when hist == kHistSparse && sidx != ~0u)
-  uint32_t id;     // entry id: the counters' index (node records: of the node's newest entry)
-  uint32_t count;  // (node records) entries of the node
-  uint32_t first;  // (node records) table position of the newest entry; the older ones follow it
-  uint64_t pad1;
-};
-static_assert(sizeof(DevEntry) == 64, "DevEntry");
 
 struct Params {
   const uint8_t* data;

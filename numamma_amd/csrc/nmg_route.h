@@ -34,58 +34,11 @@
 
 #include "nmg_kernels.h"
 #include "nmg_pool_layout.h"
+#include "nmg_table_build.h"
 
 namespace nmg {
 
 constexpr uint32_t kChunk = 64;            // compact records per chunk (one wave processes one chunk)
-constexpr uint32_t kPartLevels = 11;
-constexpr uint32_t kMaxParts = (1u << kPartLevels) - 1;
-// route pass: a sample's partition from a directory over the partition starts
-// (RSeg): its segment by comparisons with the segment starts (kernel
-// arguments), its slot's entry (u16: last partition starting at or before the
-// slot start | starts inside the slot << 11, 31 = to the segment's end), then
-// a binary search over those few starts (sorted, in LDS)
-constexpr uint32_t kRouteDir = 4096;
-constexpr uint32_t kRouteSegs = 8;
-constexpr uint32_t kDirCntSat = 31;
-struct RSeg {
-  uint64_t start;   // first partition start of the segment (~0: unused)
-  uint32_t base;    // first directory slot
-  uint32_t nslots;  // slots (>= 1)
-  uint32_t shift;   // slot j covers [start + (j << shift), + 2^shift); the last slot: to the next segment
-  uint32_t qlast;   // last partition of the segment
-};
-constexpr uint32_t kPartKeys = 1023;       // local pass: keys per partition in LDS (sorted)
-constexpr uint32_t kPartSlots = 1024;      // per-partition table stride
-constexpr uint32_t kPartDir = 1024;        // directory slots per partition (radix over its key span)
-// PartDir, one directory slot (16 B): x = largest key index <= slot start
-// (10 bits) | keys inside the slot (11) << 10 | inline (1) << 21; y, z, w =
-// the first kDirInline inner keys' offsets from the slot start (u16 pairs,
-// 0xffff past the count), valid when `inline` (every listed offset < 2^16):
-// a lookup counts the offsets <= its own and reads keys only past them
-constexpr uint32_t kDirInline = 6;
-// PackedNode, a key's newest entry for the local pass's common path (16 B):
-//   x = end - first key, y = alloc_q, z = free_q, w = table position - e0
-//   (11 bits) | kPnOlder | kPnExact | kPnOldLds | older entries << kPnOldShift
-// with alloc_q / free_q = (date - tbase) >> kPnQShift, saturated to 32 bits
-// (an entry freed before tbase: alloc_q = ~0, free_q = 0, no sample
-// matches); pe_info.y = buffer_addr - first key.  A sample whose quantised
-// timestamp equals either bound, or a key marked exact (its object's start or
-// end offset needs more than 32 bits), is decided on the exact node record.
-constexpr uint32_t kPnQShift = 8;
-constexpr uint32_t kPnOlder = 1u << 11, kPnExact = 1u << 12;
-// The older entries of a partition's reused keys (the LIFO chain past the
-// newest, tools/hash.c:108-114), in table order, up to kOldLds per partition:
-// x = end - first key, y = alloc_q, z = free_q, w = buffer_addr - first key
-// (an entry freed before tbase: all zero but y = ~0), and per entry its page
-// cell (pe_oinf, as PartInfo's info.x).  A key has them in the list
-// (kPnOldLds) when all fit: the list index of its i-th older entry is its
-// table position - e0 - key index + i - 1.  Otherwise, or when a quantised
-// date is ambiguous, the lookup walks the chain in global memory.
-constexpr uint32_t kOldLds = 512;
-constexpr uint32_t kPnOldLds = 1u << 13, kPnOldShift = 16;
-constexpr uint32_t kPartEntries = 1536;    // entries per partition (LDS object counters)
-constexpr uint32_t kPartCells = 28672;     // u16 page cells per partition: nb_threads x cell span
 constexpr uint32_t kItemChunks = 1023;     // chunks per work item (one workgroup): fewer than 2^16 records, so
                                            // neither the packed object counters nor a u16 page cell can
                                            // overflow before the item's flush
@@ -120,21 +73,6 @@ constexpr int kRouteTimingWords = 16;            // route2: wait, check+loads, g
                                                  // direct, lap waits, windows, broken, line rounds, stores
                                                  // -, windows, -, -
 
-// One partition: keys [k0, k0 + nk), entries [e0, e0 + ne) (entry ids of the
-// offline table are table positions, so a key range owns an id range), dense
-// page cells [cb, cb + span) of every thread.
-struct PartInfo {
-  uint32_t k0, nk, e0, ne;
-  uint64_t cb;
-  uint32_t span;
-  uint32_t dshift;     // directory slot j covers [first key + (j << dshift), + 2^dshift)
-  uint32_t pages_lds;  // nb_threads * span <= kPartCells: page cells in LDS, else global atomics
-  uint32_t cmap;       // ~0: cells [cb, cb + span); else (online table) span packed cells, the
-                       // histogram cell of packed cell j at pe_cmap[cmap + j]
-  uint32_t pad[2];
-};
-static_assert(sizeof(PartInfo) == 48, "PartInfo");
-
 // compact record: 16 B, two u64 words (everything the local pass needs; the
 // global counters were done by the route pass)
 //   lo = addr - partition start (kAddrBits) | (ts - tbase) << kAddrBits (low 24 bits)
@@ -145,7 +83,6 @@ static_assert(sizeof(PartInfo) == 48, "PartInfo");
 //        | thread rank << (63 - tbits) | access type << 63
 // A record whose address, timestamp or weight does not fit carries wesc: the
 // local pass re-reads all three from the raw record (rare).
-constexpr uint32_t kAddrBits = 40;
 // narrowest weight field of a compact record: weights up to 2046 cycles (the
 // bulk of PEBS load latencies) never escape; a buffer set whose location
 // fields leave fewer bits keeps the single-pass kernel (route_layout)

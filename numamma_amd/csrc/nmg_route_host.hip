@@ -24,7 +24,7 @@ bool route_layout(nmg_engine* h, const std::vector<BufDesc>& descs, XLayout& xl)
   if (loc > 48 - kMinWeightBits || xl.gbits > 31 || xl.obits > 31 || xl.tbits > 31) return false;
   xl.wbits = std::min<uint32_t>(48 - loc, 16);  // (the decode reads at most 16 bits of weight)
   xl.wesc = (1ull << xl.wbits) - 1;
-  xl.tbase = h->route_tbase;
+  xl.tbase = h->rt.tbase;
   return true;
 }
 
@@ -188,8 +188,8 @@ int route_analyze_job(nmg_engine* h, const RouteJob& job) {
   rp.pbounds = h->rt.d_pbounds;
   rp.pdir = h->rt.d_pdir;
   rp.pdead = h->rt.d_pdead;
-  for (uint32_t k = 0; k < kRouteSegs; k++) rp.seg[k] = h->rsegs[k];
-  rp.nseg = h->nrsegs;
+  for (uint32_t k = 0; k < kRouteSegs; k++) rp.seg[k] = h->rt.rsegs[k];
+  rp.nseg = h->rt.nrsegs;
   rp.nparts = h->rt.nparts;
   rp.xl = xl;
   rp.seq0 = seq0;

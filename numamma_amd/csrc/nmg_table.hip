@@ -4,64 +4,20 @@
 // partition-first path's partitions, and online table updates.
 #include "nmg_engine_impl.h"
 
-// Lookup structure of a table larger than kLdsNodes keys (see lower_key):
-// fence b = keys[b << fence_log2] (<= kMaxFences fences, Eytzinger order),
-// and per bucket a directory of 2^dir_log2 equal-width slots over the bucket's
-// key span [first key, last key].
-struct BigLookup {
-  uint32_t nb_fences = 0, fence_log2 = 0, dir_log2 = 0;
-  std::vector<uint64_t> efences;  // [kMaxFences + 1]
-  std::vector<uint8_t> shift;     // [nb_fences]
-  std::vector<uint2> dir;         // [nb_fences << dir_log2]
-};
-
-static void build_big_lookup(const uint64_t* keys, uint32_t K, bool no_dir, BigLookup& bl) {
-  while (((uint64_t)K + (1u << bl.fence_log2) - 1) >> bl.fence_log2 > kMaxFences) bl.fence_log2++;
-  const uint32_t S = 1u << bl.fence_log2;
-  bl.nb_fences = (uint32_t)(((uint64_t)K + S - 1) >> bl.fence_log2);
-  // Eytzinger order: an in-order walk of the complete 12-level tree hands out
-  // the fences in sorted order; the slots after the last fence hold ~0
-  bl.efences.assign(kMaxFences + 1, ~0ull);
-  {
-    uint32_t r = 0, i = 1;
-    std::vector<uint32_t> stack;
-    while (i <= kMaxFences || !stack.empty()) {
-      while (i <= kMaxFences) {
-        stack.push_back(i);
-        i = 2 * i;
-      }
-      i = stack.back();
-      stack.pop_back();
-      if (r < bl.nb_fences) bl.efences[i] = keys[(uint64_t)r << bl.fence_log2];
-      r++;
-      i = 2 * i + 1;
-    }
-  }
-  bl.shift.assign(bl.nb_fences, kShiftSearch);
-  // bucket-relative indices and counts are 16-bit: S <= 2^16 (larger
-  // buckets -- more than 4095 << 16 keys -- are binary-searched)
-  if (S == 1 || S > (1u << 16) || no_dir) return;
-  bl.dir_log2 = bl.fence_log2 + 1;  // two slots per key
-  const uint32_t D = 1u << bl.dir_log2;
-  bl.dir.assign((size_t)bl.nb_fences << bl.dir_log2, make_uint2(0, 0));
-  for (uint32_t b = 0; b < bl.nb_fences; b++) {
-    const uint32_t k0 = b * S, k1 = std::min<uint64_t>((uint64_t)k0 + S, K);
-    const uint64_t f = keys[k0], span = keys[k1 - 1] - f;
-    uint32_t sh = 0;
-    while (sh < 64 && (span >> sh) >= D) sh++;
-    if (sh > 32) continue;  // slot offsets must fit 32 bits: binary search instead
-    bl.shift[b] = (uint8_t)sh;
-    uint2* dd = &bl.dir[(size_t)b << bl.dir_log2];
-    uint32_t k = k0;  // largest key <= slot start
-    for (uint32_t j = 0; j < D; j++) {
-      const uint64_t s0 = (uint64_t)j << sh;  // slot [s0, s0 + 2^sh) relative to f; the last slot is open
-      while (k + 1 < k1 && keys[k + 1] - f <= s0) k++;
-      uint32_t c = 0;
-      while (k + 1 + c < k1 && (j == D - 1 || keys[k + 1 + c] - f < s0 + (1ull << sh))) c++;
-      dd[j].x = (k - k0) | (std::min<uint32_t>(c, 0xffffu) << 16);
-      dd[j].y = c ? (uint32_t)(keys[k + 1] - f - s0) : 0u;
-    }
-  }
+// The builders' 8 B and 16 B words (nmg_table_build.h) are what the kernels
+// read as uint2 and uint4
+static_assert(sizeof(Word8) == sizeof(uint2) && offsetof(Word8, x) == offsetof(uint2, x) &&
+                  offsetof(Word8, y) == offsetof(uint2, y),
+              "Word8 is uint2");
+static_assert(sizeof(Word16) == sizeof(uint4) && offsetof(Word16, x) == offsetof(uint4, x) &&
+                  offsetof(Word16, y) == offsetof(uint4, y) && offsetof(Word16, z) == offsetof(uint4, z) &&
+                  offsetof(Word16, w) == offsetof(uint4, w),
+              "Word16 is uint4");
+static hipError_t alloc_copy(nmg_engine* h, DevBuf<uint2>& b, const std::vector<Word8>& src) {
+  return alloc_copy(h, b, reinterpret_cast<const uint2*>(src.data()), src.size());
+}
+static hipError_t alloc_copy(nmg_engine* h, DevBuf<uint4>& b, const std::vector<Word16>& src) {
+  return alloc_copy(h, b, reinterpret_cast<const uint4*>(src.data()), src.size());
 }
 
 // Lookup structures of a flattened table whose entries, in table order, are
@@ -71,51 +27,18 @@ static void build_big_lookup(const uint64_t* keys, uint32_t K, bool no_dir, BigL
 int build_lookup(nmg_engine* h, LookupSet& l, const uint64_t* keys, const uint32_t* entry_off, uint32_t nb_keys,
                  const std::vector<DevEntry>& chain, DevEntry* chain_dev) {
   l.K = nb_keys;
-  std::vector<DevEntry> nodes(nb_keys);
-  for (uint32_t k = 0; k < nb_keys; k++) {
-    nodes[k] = chain[entry_off[k]];
-    nodes[k].first = entry_off[k];
-    nodes[k].count = entry_off[k + 1] - entry_off[k];
-  }
+  const std::vector<DevEntry> nodes = node_records(entry_off, nb_keys, chain);
   HIP_TRY(h, alloc_copy(h, l.keys, keys, nb_keys));
   HIP_TRY(h, alloc_copy(h, l.nodes, nodes));
   if (!chain_dev) HIP_TRY(h, alloc_copy(h, l.own_chain, chain));
   l.chain = chain_dev ? chain_dev : l.own_chain.get();
+  l.elevels = l.nb_fences = l.fence_log2 = l.dir_log2 = 0;
   if (nb_keys <= kLdsNodes) {
-    // Eytzinger (BFS) order for the LDS search: an in-order walk of the
-    // complete tree of 2^L - 1 nodes hands out the keys in sorted order; the
-    // slots after the last key are ~0 keys carrying a copy of the last node
-    // (reached only for addr == UINT64_MAX, where the last key is the answer)
-    l.elevels = 0;
-    while (((1u << l.elevels) - 1) < nb_keys) l.elevels++;
-    const uint32_t n = 1u << l.elevels;
-    std::vector<uint64_t> ef(n, ~0ull);
-    std::vector<DevEntry> en(n);
-    memset(en.data(), 0, n * sizeof(DevEntry));
-    uint32_t r = 0;
-    std::vector<uint32_t> stack;
-    uint32_t i = 1;
-    while (i < n || !stack.empty()) {  // iterative in-order walk
-      while (i < n) {
-        stack.push_back(i);
-        i = 2 * i;
-      }
-      i = stack.back();
-      stack.pop_back();
-      if (r < nb_keys) {
-        ef[i] = keys[r];
-        en[i] = nodes[r];
-      } else if (nb_keys) {
-        en[i] = nodes[nb_keys - 1];
-      }
-      r++;
-      i = 2 * i + 1;
-    }
-    HIP_TRY(h, alloc_copy(h, l.efences, ef));
-    HIP_TRY(h, alloc_copy(h, l.enodes, en));
-  }
-  l.nb_fences = l.fence_log2 = l.dir_log2 = 0;
-  if (nb_keys > kLdsNodes) {
+    const SmallLookup sl = build_small_lookup(keys, nb_keys, nodes);
+    l.elevels = sl.elevels;
+    HIP_TRY(h, alloc_copy(h, l.efences, sl.ekeys));
+    HIP_TRY(h, alloc_copy(h, l.enodes, sl.enodes));
+  } else {
     BigLookup bl;
     build_big_lookup(keys, nb_keys, (h->flags & kDbgNoDir) != 0, bl);
     l.nb_fences = bl.nb_fences;
@@ -128,287 +51,44 @@ int build_lookup(nmg_engine* h, LookupSet& l, const uint64_t* keys, const uint32
   return NMG_OK;
 }
 
-// The route pass's partition search (route_partition, nmg_route.hip) over
-// the P ascending partition starts b: up to kRouteSegs segments, split at the
-// gaps between consecutive starts that dwarf the median gap (address spaces
-// are clustered: globals, heap, mmap'd regions, the stack), each with
-// directory slots in proportion to its partitions.  Slot j of a segment holds
-// the last partition starting at or before the slot start, and how many
-// starts lie inside the slot (saturated at kDirCntSat: search to the
-// segment's last partition).
-void route_segments(const uint64_t* b, uint32_t P, RSeg* seg, uint32_t* nseg, std::vector<uint16_t>& dir) {
-  std::vector<uint32_t> cuts{0};  // segment k starts at partition cuts[k]
-  if (P > 1) {
-    std::vector<uint64_t> gaps(P - 1);
-    for (uint32_t q = 0; q + 1 < P; q++) gaps[q] = b[q + 1] - b[q];
-    std::vector<uint64_t> med(gaps);
-    std::nth_element(med.begin(), med.begin() + med.size() / 2, med.end());
-    const uint64_t m = std::max<uint64_t>(med[med.size() / 2], 1);
-    std::vector<uint32_t> idx(P - 1);
-    for (uint32_t q = 0; q + 1 < P; q++) idx[q] = q;
-    std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return gaps[x] > gaps[y]; });
-    for (uint32_t i = 0; i < idx.size() && cuts.size() < kRouteSegs; i++) {
-      if (gaps[idx[i]] / 64 <= m) break;
-      cuts.push_back(idx[i] + 1);
-    }
-    std::sort(cuts.begin(), cuts.end());
-  }
-  const uint32_t S = (uint32_t)cuts.size();
-  dir.assign(kRouteDir, 0);
-  uint32_t used = 0;
-  for (uint32_t k = 0; k < kRouteSegs; k++) {
-    if (k >= S) {
-      seg[k] = RSeg{~0ull, 0, 1, 0, 0};
-      continue;
-    }
-    const uint32_t qa = cuts[k], qb = k + 1 < S ? cuts[k + 1] : P;
-    const uint32_t ns = (uint32_t)((uint64_t)(kRouteDir - S) * (qb - qa) / P) + 1;
-    const uint64_t span = b[qb - 1] - b[qa];
-    uint32_t sh = 0;
-    while (sh < 63 && (span >> sh) >= ns) sh++;
-    seg[k] = RSeg{b[qa], used, ns, sh, qb - 1};
-    uint32_t q = qa;
-    for (uint32_t j = 0; j < ns; j++) {
-      // slot [s0, s1) relative to the segment start
-      const unsigned __int128 s0 = (unsigned __int128)j << sh, s1 = (unsigned __int128)(j + 1) << sh;
-      while (q + 1 < qb && (unsigned __int128)(b[q + 1] - b[qa]) <= s0) q++;
-      uint32_t c = 0;
-      if (j == ns - 1) c = qb - 1 - q;
-      else
-        while (q + 1 + c < qb && (unsigned __int128)(b[q + 1 + c] - b[qa]) < s1) c++;
-      dir[used + j] = (uint16_t)(q | (std::min(c, kDirCntSat) << 11));
-    }
-    used += ns;
-  }
-  *nseg = S;
-}
-
-// Partitions of the partition-first path (nmg_route.h): runs of consecutive
-// keys, each at most kPartKeys keys and kPartEntries entries, and -- where
-// the keys allow it -- at most kPartCells dense page cells over all threads,
-// so that a partition's lookup tree, node records, object counters and page
-// cells fit one workgroup's LDS.  A key range owns a range of table
-// positions; `ids` (an online table, nmg_update_objects) maps a position to
-// its entry id (null: the id is the position).  An online table's entries
-// have their page cells in id order, scattered over the address order, so
-// its partitions are not cut by cells (the cells of a partition whose span is
-// too wide for LDS take global atomics).  Only for engines that count per
-// object (NMG_F_MATCH_SAMPLES); the dump modes' per-sample output and the
-// per-object levels are outputs of the local pass too (local_kernel's extras).
+// The partition-first path's tables (build_part_tables) of the table whose
+// entries, in table order, are dev[]; `ids`: an online table's entry id per
+// table position (nmg_update_objects), else null.  NMG_OK with h->rt.ok false:
+// the table keeps the single-pass attribute_kernel.  Only for engines that
+// count per object (NMG_F_MATCH_SAMPLES); the dump modes' per-sample output and
+// the per-object levels are outputs of the local pass too (local_kernel's
+// extras).  The engine's route table is replaced once every upload succeeded.
 int build_partitions(nmg_engine* h, const uint64_t* keys, const uint32_t* entry_off, uint32_t K,
-                            const std::vector<DevEntry>& dev, const uint32_t* ids) {
+                     const std::vector<DevEntry>& dev, const uint32_t* ids) {
   h->rt = RouteTable();
-  if (K <= kLdsNodes || !(h->flags & NMG_F_MATCH_SAMPLES)) return NMG_OK;
-  if (ids) {  // the identity map is the offline case
-    uint32_t e = 0;
-    while (e < entry_off[K] && ids[e] == e) e++;
-    if (e == entry_off[K]) ids = nullptr;
-  }
-  if (ids && h->tab.cells() >= (1ull << 31)) return NMG_OK;  // (cell indices of an online table: 32-bit)
-  const uint64_t T = h->T;
-  std::vector<PartInfo> parts;
-  // an online table: the partition's dense cells packed in LDS in table
-  // order (lrel: an entry's first LDS cell per table position; cmap: the
-  // histogram cell of every packed cell, per partition from PartInfo::cmap)
-  std::vector<uint32_t> lrel, cmap;
-  if (ids) lrel.assign(entry_off[K], kEmpty32);
-  uint32_t k = 0;
-  while (k < K) {
-    PartInfo pi;
-    memset(&pi, 0, sizeof(pi));
-    pi.k0 = k;
-    pi.e0 = entry_off[k];
-    pi.cmap = ~0u;
-    uint64_t cb = ~0ull, ce = 0, cc = 0;  // dense cells in [cb, ce), cc of them
-    while (k < K && k - pi.k0 < kPartKeys) {
-      // a partition's keys span less than 2^(kAddrBits - 1) bytes, so that the
-      // compact records' address field (relative to the partition's first key)
-      // holds every address its objects cover: a run of keys across a wide gap
-      // in the address space (the heap, then the stack) starts a new partition
-      if (k > pi.k0 && keys[k] - keys[pi.k0] >= (1ull << (kAddrBits - 1))) break;
-      const uint32_t ea = entry_off[k], eb = entry_off[k + 1];
-      if (eb - pi.e0 > kPartEntries) {
-        if (k == pi.k0) return NMG_OK;  // one address reused more than kPartEntries times: keep attribute_kernel
-        break;
-      }
-      uint64_t ncb = cb, nce = ce, ncc = cc;
-      for (uint32_t e = ea; e < eb; e++)
-        if (dev[e].hist != kHistSparse) {
-          const uint64_t np = h->tab.npages[dev[e].id];
-          ncb = std::min<uint64_t>(ncb, dev[e].hist);
-          nce = std::max<uint64_t>(nce, dev[e].hist + np);
-          ncc += np;
-        }
-      if (k > pi.k0 && ncb != ~0ull && (ids ? ncc : nce - ncb) * T > kPartCells)
-        break;  // (one key alone may exceed: global cells)
-      cb = ncb;
-      ce = nce;
-      cc = ncc;
-      k++;
-    }
-    pi.nk = k - pi.k0;
-    pi.ne = entry_off[k] - pi.e0;
-    pi.cb = cb == ~0ull ? 0 : cb;
-    pi.span = cb == ~0ull ? 0 : (uint32_t)(ce - cb);
-    pi.pages_lds = pi.span && (uint64_t)pi.span * T <= kPartCells;
-    if (ids && cc && cc * T <= kPartCells) {  // online: the cells packed (cmap), always in LDS
-      pi.cmap = (uint32_t)cmap.size();
-      pi.span = (uint32_t)cc;
-      pi.pages_lds = 1;
-      uint32_t off = 0;
-      for (uint32_t e = pi.e0; e < pi.e0 + pi.ne; e++)
-        if (dev[e].hist != kHistSparse) {
-          const uint32_t np = (uint32_t)h->tab.npages[dev[e].id];
-          lrel[e] = off;
-          for (uint32_t g = 0; g < np; g++) cmap.push_back((uint32_t)(dev[e].hist + g));
-          off += np;
-        }
-    }
-    const uint64_t kspan = keys[k - 1] - keys[pi.k0];
-    while (pi.dshift < 63 && (kspan >> pi.dshift) >= kPartDir) pi.dshift++;
-    parts.push_back(pi);
-    if (parts.size() > kMaxParts) return NMG_OK;  // too many partitions for the route pass's LDS tree
-  }
-  const uint32_t P = (uint32_t)parts.size();
-  // the compact records' timestamp base: the earliest allocation (a sample
-  // before it can only match objects allocated at time 0, and escapes)
-  h->route_tbase = ~0ull;
-  for (const DevEntry& d : dev)
-    if (d.alloc) h->route_tbase = std::min<uint64_t>(h->route_tbase, d.alloc);
-  if (h->route_tbase == ~0ull) h->route_tbase = 0;
-  // per partition: keys ascending with their newest entry's node record (the
-  // exact one, read by the local pass's rare paths), its packed form and
-  // info (the common path), and a directory over the key span: slot j starts
-  // at first key + (j << dshift) and holds the index of the largest key <=
-  // that start, the number of keys inside the slot (the last slot: every key
-  // after its start) and the first kDirInline of those keys' offsets from the
-  // slot start when they fit 16 bits (PartDir)
-  const uint64_t tb = h->route_tbase;
-  std::vector<uint64_t> pk((size_t)P * kPartSlots, ~0ull);
-  std::vector<uint4> pn((size_t)P * kPartSlots * 2, make_uint4(0, 0, 0, 0));
-  std::vector<uint4> ppn((size_t)P * kPartSlots, make_uint4(0, 0, 0, 0));
-  std::vector<uint2> pinf((size_t)P * kPartSlots, make_uint2(kEmpty32, 0));
-  std::vector<uint4> pdir((size_t)P * kPartDir, make_uint4(0, 0, 0, 0));
-  std::vector<uint4> pold((size_t)P * kOldLds, make_uint4(0, 0, 0, 0));
-  std::vector<uint32_t> poinf((size_t)P * kOldLds, kEmpty32);
-  // an entry's page cell relative to its partition (as pe_info.x)
-  auto cell_rel = [&](const PartInfo& pi, uint32_t e) -> uint32_t {
-    const DevEntry& d = dev[e];
-    return d.hist == kHistSparse ? kEmpty32 : pi.cmap != ~0u ? lrel[e] : (uint32_t)(d.hist - pi.cb);
-  };
-  // the quantised dates of an entry (never matching: ~0, 0)
-  auto qdates = [&](const DevEntry& d, uint64_t tb, uint32_t& aq, uint32_t& fq) {
-    if (d.free < tb) {
-      aq = 0xffffffffu;
-      fq = 0;
-    } else {
-      aq = (uint32_t)std::min<uint64_t>((d.alloc > tb ? d.alloc - tb : 0) >> kPnQShift, 0xffffffffull);
-      fq = (uint32_t)std::min<uint64_t>((d.free - tb) >> kPnQShift, 0xffffffffull);
-    }
-  };
-  for (uint32_t q = 0; q < P; q++) {
-    const PartInfo& pi = parts[q];
-    const uint64_t f = keys[pi.k0];
-    for (uint32_t r = 0; r < pi.nk; r++) {
-      const uint32_t kk = pi.k0 + r;
-      const DevEntry& d = dev[entry_off[kk]];
-      const size_t o = (size_t)q * kPartSlots + r;
-      pk[o] = keys[kk];
-      pn[2 * o] = make_uint4((uint32_t)d.addr, (uint32_t)(d.addr >> 32), (uint32_t)d.end, (uint32_t)(d.end >> 32));
-      pn[2 * o + 1] = make_uint4((uint32_t)d.alloc, (uint32_t)(d.alloc >> 32), (uint32_t)d.free, (uint32_t)(d.free >> 32));
-      const uint32_t older = entry_off[kk + 1] - entry_off[kk] > 1 ? 1u : 0u;
-      const uint32_t hrel = cell_rel(pi, entry_off[kk]);
-      // packed node (PackedNode): exact where the object's start or end
-      // offset from the first key needs more than 32 bits -- unless it was
-      // freed before the first allocation (the [stack], Q4): no non-escaped
-      // sample can match it, whatever its bounds
-      const uint64_t erel = d.end - f, brel = d.addr - f;
-      const bool never = d.free < tb;
-      const bool exact = !never && (d.addr < f || d.end < d.addr || (erel >> 32) != 0 || (brel >> 32) != 0);
-      uint32_t aq, fq;
-      qdates(d, tb, aq, fq);
-      // the key's older entries in the partition's list (kOldLds) when they fit
-      const uint32_t nold = entry_off[kk + 1] - entry_off[kk] - 1, lbase = entry_off[kk] - pi.e0 - r;
-      bool old_lds = nold > 0 && nold < 2048 && lbase + nold <= kOldLds;
-      for (uint32_t i = 1; old_lds && i <= nold; i++) {
-        const uint32_t e = entry_off[kk] + i;
-        const DevEntry& od = dev[e];
-        uint32_t oa, of;
-        qdates(od, tb, oa, of);
-        uint4 v = make_uint4(0, oa, of, 0);
-        if (od.free >= tb) {  // (else: never matches, bounds irrelevant)
-          if (od.addr < f || od.end < od.addr || ((od.end - f) >> 32) != 0) {
-            old_lds = false;
-            break;
-          }
-          v.x = (uint32_t)(od.end - f);
-          v.w = (uint32_t)(od.addr - f);
-        }
-        pold[(size_t)q * kOldLds + lbase + i - 1] = v;
-        poinf[(size_t)q * kOldLds + lbase + i - 1] = cell_rel(pi, e);
-      }
-      ppn[o] = make_uint4(exact || never ? 0u : (uint32_t)erel, aq, fq,
-                          (entry_off[kk] - pi.e0) | (older ? kPnOlder : 0u) | (exact ? kPnExact : 0u) |
-                              (old_lds ? kPnOldLds | (nold << kPnOldShift) : 0u));
-      pinf[o] = make_uint2(hrel, exact || never ? 0u : (uint32_t)brel);
-    }
-    uint32_t lo = 0;
-    for (uint32_t j = 0; j < kPartDir; j++) {
-      const uint64_t s0 = (uint64_t)j << pi.dshift;  // slot start relative to the first key
-      while (lo + 1 < pi.nk && keys[pi.k0 + lo + 1] - f <= s0) lo++;
-      uint32_t c = 0;
-      while (lo + 1 + c < pi.nk &&
-             (j == kPartDir - 1 || keys[pi.k0 + lo + 1 + c] - f < s0 + (1ull << pi.dshift)))
-        c++;
-      uint32_t off[kDirInline];
-      bool inl = true;
-      for (uint32_t i = 0; i < kDirInline; i++) {
-        off[i] = 0xffffu;
-        if (i < c) {
-          const uint64_t v = keys[pi.k0 + lo + 1 + i] - f - s0;
-          if (v >> 16) inl = false;
-          else off[i] = (uint32_t)v;
-        }
-      }
-      pdir[(size_t)q * kPartDir + j] =
-          make_uint4(lo | (c << 10) | ((inl && c ? 1u : 0u) << 21), off[0] | (off[1] << 16), off[2] | (off[3] << 16),
-                     off[4] | (off[5] << 16));
-    }
-  }
-  // the route pass's partition search: the partitions' first keys ascending,
-  // and a directory over them (route_segments)
-  std::vector<uint64_t> pb(kMaxParts + 1, ~0ull);
-  for (uint32_t q = 0; q < P; q++) pb[q] = keys[parts[q].k0];
-  std::vector<uint16_t> rdir;
-  route_segments(pb.data(), P, h->rsegs, &h->nrsegs, rdir);
-  // partitions whose entries all have free_date 0 (RouteParams::pdead): the
-  // route pass keeps only their timestamp-0 samples, the others cannot match
-  std::vector<uint32_t> dead((kMaxParts + 1) / 32, 0u);
-  for (uint32_t q = 0; q < P; q++) {
-    bool d = true;
-    for (uint32_t e = parts[q].e0; d && e < parts[q].e0 + parts[q].ne; e++) d = dev[e].free == 0;
-    if (d) dead[q >> 5] |= 1u << (q & 31);
-  }
-  RouteTable& rt = h->rt;
-  HIP_TRY(h, alloc_copy(h, rt.d_pdead, dead));
-  HIP_TRY(h, alloc_copy(h, rt.d_parts, parts));
-  HIP_TRY(h, alloc_copy(h, rt.d_pbounds, pb));
-  HIP_TRY(h, alloc_copy(h, rt.d_pdir, rdir));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_keys, pk));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_nodes, pn));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_pnode, ppn));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_old, pold));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_oinf, poinf));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_info, pinf));
-  HIP_TRY(h, alloc_copy(h, rt.d_pe_dir, pdir));
-  if (ids) {
+  if (!(h->flags & NMG_F_MATCH_SAMPLES)) return NMG_OK;
+  const PartTables pt =
+      build_part_tables(TableInput{keys, entry_off, K, dev.data(), h->tab.npages.data(), ids, h->T, h->tab.cells()});
+  if (!pt.ok) return NMG_OK;
+  RouteTable rt;
+  HIP_TRY(h, alloc_copy(h, rt.d_pdead, pt.pdead));
+  HIP_TRY(h, alloc_copy(h, rt.d_parts, pt.parts));
+  HIP_TRY(h, alloc_copy(h, rt.d_pbounds, pt.pbounds));
+  HIP_TRY(h, alloc_copy(h, rt.d_pdir, pt.route.dir));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_keys, pt.pe_keys));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_nodes, pt.pe_nodes));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_pnode, pt.pe_pnode));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_old, pt.pe_old));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_oinf, pt.pe_oinf));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_info, pt.pe_info));
+  HIP_TRY(h, alloc_copy(h, rt.d_pe_dir, pt.pe_dir));
+  if (pt.online) {
     HIP_TRY(h, alloc_copy(h, rt.d_pe_ids, ids, entry_off[K]));
-    HIP_TRY(h, alloc_copy(h, rt.d_pe_lrel, lrel));
-    if (!cmap.empty()) HIP_TRY(h, alloc_copy(h, rt.d_pe_cmap, cmap));
+    HIP_TRY(h, alloc_copy(h, rt.d_pe_lrel, pt.pe_lrel));
+    if (!pt.pe_cmap.empty()) HIP_TRY(h, alloc_copy(h, rt.d_pe_cmap, pt.pe_cmap));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (pageable sources)
-  rt.nparts = P;
+  std::copy(pt.route.seg, pt.route.seg + kRouteSegs, rt.rsegs);
+  rt.nrsegs = pt.route.nseg;
+  rt.tbase = pt.tbase;
+  rt.nparts = pt.nparts;
   rt.ok = true;
+  h->rt = std::move(rt);
   return NMG_OK;
 }
 

@@ -11,8 +11,10 @@ chunks have the shapes where that can go wrong.  Every replay is one buffer
 over a table of 1,100 to 3,000 intervals.
 
 Nothing here calls the engine.  The partition cut and the per-partition
-directory are restated from build_partitions (nmg_table.hip), for tables whose
-page cells can never cut a partition (asserted by `partitions`)."""
+directory are restated from cut_partitions and build_part_dir
+(numamma_amd/csrc/nmg_table_build.h), for tables whose page cells can never
+cut a partition (asserted by `partitions`); test_table_build_host.py holds the
+restatement against what those builders make."""
 import copy
 import dataclasses
 

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]
 
 
-def _build_and_run(name, d, extra=()):
+def _build_and_run(name, d, extra=(), args=()):
     cxx = shutil.which(os.environ.get("CXX", "g++"))
     assert cxx, "no C++ compiler"
     exe = os.path.join(d, name)
@@ -32,7 +32,7 @@ def _build_and_run(name, d, extra=()):
                         os.path.join(ROOT, "tests", "c", name + ".cpp"), "-o", exe], capture_output=True, text=True)
     if r.returncode:
         return None, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert name + ": ok" in r.stdout
     return r.stdout, ""
