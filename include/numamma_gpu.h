@@ -333,7 +333,8 @@ int nmg_get_page_cells(nmg_engine *h, uint32_t *rows /* [n][4] */, int64_t n);
  * the clamp keeps every matched sample of a selected entry in exactly one
  * cell, so the cells summed over the bins are the entry's page cells grouped
  * by row.  An entry is selected when its page histogram is dense (huge ranges
- * such as [stack] are not) and its buffer_size >= min_object_bytes; it takes
+ * such as [stack] are not: nmg_set_timeline_ex with NMG_TL_SCOPE_ALL, below,
+ * selects them too) and its buffer_size >= min_object_bytes; it takes
  * nb_bins * nb_threads * R cells, R = (buffer_size / 4096 + 1 + 2^row_shift - 1)
  * >> row_shift, at most 2^32 - 1 cells in all.
  * nmg_set_timeline lays the cells out and zeroes them: after nmg_set_objects,
@@ -359,6 +360,41 @@ struct nmg_timeline_options {
   uint64_t budget_bytes;     /* cap on the cell array (0: default 1 GiB) */
 };
 int nmg_set_timeline(nmg_engine *h, const struct nmg_timeline_options *tl);
+/* nmg_set_timeline_ex: the same with the entries chosen.  NMG_TL_SCOPE_DENSE is
+ * nmg_set_timeline(h, tl) itself.  With NMG_TL_SCOPE_ALL an entry is selected
+ * iff buffer_size >= min_object_bytes, dense or sparse -- [stack], arrays of
+ * more than 2^24 page cells and whatever hist_budget_bytes left sparse too.  A
+ * dense selected entry keeps its [bin][thread][row] block.  A sparse one keeps
+ * only its non-zero cells, in a second open-addressed table on the device (the
+ * timeline sparse table): key (ordinal of the selected sparse entry in id
+ * order, bin, thread, row) -> u32 count, the bin by the rule above, the row
+ * the 32-bit page number under which the entry's page count is kept >>
+ * row_shift.  The invariant above then holds for every selected entry: its
+ * cells summed over the bins are its page cells (nmg_get_page_cells) grouped
+ * by row.  [stack] matches only ts = 0 samples (quirk Q4), so its cells all lie
+ * in bin 0 whenever t0 > 0.
+ * The table has the engine's sparse_capacity slots (nmg_options) of 12 bytes,
+ * is allocated only when a sparse entry is selected, and counts in
+ * budget_bytes beside the dense cells (NMG_ERR_CAPACITY with the bytes needed
+ * in the error detail).  At most 1023 sparse entries can be selected
+ * (NMG_ERR_CAPACITY with their number: raise min_object_bytes or the engine's
+ * hist_budget_bytes).  A table that fills during an analysis makes that
+ * analysis return NMG_ERR_CAPACITY, as the sparse page table does.  Any other
+ * scope is NMG_ERR_INVALID; every other precondition and error is
+ * nmg_set_timeline's (a multi-GPU handle is refused).
+ * The dense cells' lifetime applies: the table accumulates over analyses,
+ * streamed chunks and alarms, nmg_reset_counters empties it,
+ * nmg_set_timeline(h, NULL) or a later nmg_set_objects drops it, and
+ * nmg_update_objects keeps its rule, so no entry changes kind under it.  Like
+ * the dense cells, the table is not carried by the results snapshot
+ * (nmg_results_begin), nmg_sparse_import, the multi-GPU merge or
+ * nmg_run_replay.  The getters return dense and sparse entries' rows in one
+ * list sorted by (entry, bin, thread, row), non-zero counts only;
+ * nmg_report_timeline gives a site its sparse members' cells too (stack sites
+ * have no file, as in nmg_report_page_cost). */
+#define NMG_TL_SCOPE_DENSE 0 /* nmg_set_timeline: entries with dense page cells */
+#define NMG_TL_SCOPE_ALL 1   /* every entry of at least min_object_bytes: the sparse ones too */
+int nmg_set_timeline_ex(nmg_engine *h, const struct nmg_timeline_options *tl, uint32_t scope);
 int64_t nmg_count_timeline_cells(nmg_engine *h);
 int nmg_get_timeline_cells(nmg_engine *h, uint32_t *rows /* [n][5] */, int64_t n);
 

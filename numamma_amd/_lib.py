@@ -163,6 +163,7 @@ NMG_COST_NA = 0x40000
 NMG_COST_REMOTE = (1 << 5) | (1 << 6)
 NMG_COST_MEMORY = (1 << 4) | NMG_COST_REMOTE
 NMG_COST_SCOPE_DENSE, NMG_COST_SCOPE_ALL = 0, 1
+NMG_TL_SCOPE_DENSE, NMG_TL_SCOPE_ALL = 0, 1
 NMG_PLACE_PAGE_COUNTS, NMG_PLACE_PAGE_COST = 0, 2
 NMG_PLACE_HUGE = 4  # flag bit beside NMG_PLACE_PAGE_COUNTS: every entry contributes, sparse cells included
 
@@ -244,6 +245,7 @@ _SIGS = {
     "nmg_count_page_cells": (C.c_int64, [H]),
     "nmg_get_page_cells": (C.c_int, [H, u32p, C.c_int64]),
     "nmg_set_timeline": (C.c_int, [H, C.POINTER(nmg_timeline_options)]),
+    "nmg_set_timeline_ex": (C.c_int, [H, C.POINTER(nmg_timeline_options), C.c_uint32]),
     "nmg_count_timeline_cells": (C.c_int64, [H]),
     "nmg_get_timeline_cells": (C.c_int, [H, u32p, C.c_int64]),
     "nmg_report_timeline": (C.c_int, [H, C.POINTER(nmg_object_meta), C.POINTER(nmg_report_options)]),

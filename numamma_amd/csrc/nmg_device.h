@@ -97,10 +97,13 @@ __device__ __forceinline__ void level_count(const Params& p, uint64_t e, uint32_
 // Access timeline (Params::tl): the cell of a matched SAMPLE with timestamp ts
 // (absolute), thread th and page `page` of an entry whose by-id record has
 // pad1 = pad (tl_pad).  Bin 0 before t0, the last bin from its start on.
+__device__ __forceinline__ uint32_t timeline_bin(const Params& p, uint64_t ts) {
+  const uint64_t d = ts < p.tl_t0 ? 0ull : (ts - p.tl_t0) >> p.tl_bin_shift;
+  return (uint32_t)min(d, (uint64_t)(p.tl_nb_bins - 1));
+}
 __device__ __forceinline__ uint32_t timeline_cell(const Params& p, uint64_t pad, uint64_t ts, uint32_t th,
                                                   uint32_t page) {
-  const uint64_t d = ts < p.tl_t0 ? 0ull : (ts - p.tl_t0) >> p.tl_bin_shift;
-  const uint32_t bin = (uint32_t)min(d, (uint64_t)(p.tl_nb_bins - 1));
+  const uint32_t bin = timeline_bin(p, ts);
   const uint32_t R = (uint32_t)(pad >> 32);
   return (uint32_t)pad + (bin * p.nb_threads + th) * R + (page >> p.tl_row_shift);
 }
@@ -137,6 +140,32 @@ __device__ __forceinline__ void set_error(const Params& p, uint64_t seq, uint32_
   uint64_t w = (seq << 40) | (uint64_t(off) << 8) | code;
   atomicMin(reinterpret_cast<unsigned long long*>(p.min64 + kFirstBase + p.nb_entries),
             (unsigned long long)w);
+}
+
+// The timeline cell of a selected sparse entry (Params::tls_keys; pad =
+// tl_pad_sparse of its ordinal): one more on the count of `key` in the
+// timeline sparse table, inserted if absent.  A CAS probe as in sparse_slot --
+// the CAS is the lookup too, a plain load of a key another XCD inserted may be
+// stale -- from the slot of a full 64-bit mix (tl_sparse_hash), then a
+// no-return u32 add.  The lane's own add, no cross-lane step: it may sit in a
+// diverged region.  A full table sets the error word (seq, off: the record),
+// as sparse_add does.
+__device__ __forceinline__ uint64_t timeline_sparse_key(const Params& p, uint64_t pad, uint64_t ts, uint32_t th,
+                                                        uint32_t page) {
+  return tl_sparse_key((uint32_t)pad, timeline_bin(p, ts), th, page >> p.tl_row_shift);
+}
+__device__ __forceinline__ void timeline_sparse_add(const Params& p, uint64_t key, uint64_t seq, uint32_t off) {
+  uint32_t slot = uint32_t(tl_sparse_hash(key)) & p.tls_mask;
+  for (uint32_t probe = 0; probe <= p.tls_mask; probe++) {
+    const unsigned long long prev =
+        atomicCAS(reinterpret_cast<unsigned long long*>(p.tls_keys + slot), ~0ull, (unsigned long long)key);
+    if (prev == ~0ull || prev == key) {
+      atomicAdd(p.tls_vals + slot, 1u);
+      return;
+    }
+    slot = (slot + 1) & p.tls_mask;
+  }
+  set_error(p, seq, off, kErrCapacity);
 }
 
 // Descend `levels` levels of an Eytzinger tree (node i has children 2i, 2i+1)

@@ -274,6 +274,11 @@ extern "C" int nmg_reset_counters(nmg_engine* h) {
   const uint32_t rgrid = (uint32_t)std::min<uint64_t>((longest + 256 * 16 - 1) / (256 * 16), (uint64_t)h->num_cus * 4);
   HIP_TRY(h, launch_reset(rgrid, h->stream, r));
   if (h->tl.on) HIP_TRY(h, hipMemsetAsync(h->tl.d_cells, 0, h->tl.ncells * 4, h->stream));
+  if (h->tl.on && h->tl.sp_cap && h->tl.sp_touched) {  // the timeline sparse table: emptied when a launch may have inserted
+    HIP_TRY(h, hipMemsetAsync(h->tl.d_sp_keys, 0xff, h->tl.sp_cap * 8, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->tl.d_sp_vals, 0, h->tl.sp_cap * 4, h->stream));
+    h->tl.sp_touched = false;
+  }
   if (h->cost.on && h->cost.d_cells)
     HIP_TRY(h, hipMemsetAsync(h->cost.d_cells, 0, h->tab.cells() * h->T * 8, h->stream));
   h->nreset++;
@@ -539,7 +544,7 @@ extern "C" int nmg_report_timeline(nmg_engine* h, const nmg_object_meta* meta, c
   if (!h->tl.on) return fail(h, NMG_ERR_STATE, "no timeline set (nmg_set_timeline)");
   return report_rows(h, h->tl.rows, timeline_prepare, [&](const nmg_host_results* res, const uint32_t* rows, int64_t n, std::string& err) {
     return write_timeline(res, meta, opts, &h->tl.opt, rows, n, err);
-  });
+  }, timeline_fill);
 }
 
 extern "C" int nmg_report_page_cost(nmg_engine* h, const nmg_object_meta* meta, const nmg_report_options* opts) {

@@ -250,6 +250,21 @@ struct Timeline {
   RowSet<uint32_t, 5> rows;  // (entry, bin, thread, row, count)
   DevBuf<uint32_t> d_cnt;    // their per-segment counts, offsets and the scan's partial sums
   DevBuf<uint64_t> d_off, d_part;
+  // NMG_TL_SCOPE_ALL: the selected sparse entries in id order (ordinal ->
+  // entry; such an entry's pad1 is tl_pad_sparse(ordinal)) and their cells, the
+  // timeline sparse table: sp_cap slots of a tl_sparse_key and a u32 count,
+  // allocated only when sp_ids is not empty.  rows.n counts dense and sparse
+  // rows; rows.d_rows holds the nd dense ones, sp_kv the table's used slots as
+  // sorted (key, count) words: timeline_fill merges the two.
+  uint32_t scope = NMG_TL_SCOPE_DENSE;
+  std::vector<uint32_t> sp_ids;
+  uint64_t sp_cap = 0;
+  DevBuf<uint64_t> d_sp_keys;
+  DevBuf<uint32_t> d_sp_vals;
+  bool sp_touched = false;  // an analysis may have inserted since the table was last cleared
+  SparseWords d_sp_ck;      // the getters' compaction
+  std::vector<uint64_t> sp_kv;
+  int64_t nd = 0;
 };
 
 // The page cost cells (nmg_set_page_cost): one u64 array parallel to the page
@@ -569,6 +584,7 @@ int decode_error_word(nmg_engine* h, uint64_t w);
 int cells_prepare(nmg_engine* h);
 int cells_fill(nmg_engine* h, const RowSet<uint32_t, 4>& s, uint32_t* rows);  // rows_get's fill for the page cells
 int timeline_prepare(nmg_engine* h);
+int timeline_fill(nmg_engine* h, const RowSet<uint32_t, 5>& s, uint32_t* rows);  // rows_get's fill for the timeline
 int cost_prepare(nmg_engine* h);
 int cost_fill(nmg_engine* h, const RowSet<uint64_t, 4>& s, uint64_t* rows);  // rows_get's fill for the page cost cells
 // What a report has before its rows: the counters downloaded, and res zeroed

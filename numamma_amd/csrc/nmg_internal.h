@@ -192,6 +192,62 @@ void place_sparse_rows(const uint64_t* kv, uint64_t n, const std::vector<uint32_
   }
 }
 
+// ---- timeline sparse table (nmg_set_timeline_ex, NMG_TL_SCOPE_ALL): the
+// timeline cells of the selected sparse entries, keyed by one 64-bit word
+//   row:32 | thread:10 << 32 | bin:12 << 42 | ordinal:10 << 54
+// ordinal: the entry's rank among the selected sparse entries, in id order,
+// 0..kTlMaxSparse - 1 -- so key order is (entry, bin, thread, row) order, and
+// the all-ones word (the table's empty marker) needs ordinal 1023 and is never
+// a key.  Host and device (constexpr, as sparse_key); tests/timeline_all_expect.py
+// mirrors it.
+constexpr uint32_t kTlMaxSparse = 1023;
+constexpr uint64_t tl_sparse_key(uint32_t ord, uint32_t bin, uint32_t th, uint32_t row) {
+  return (uint64_t(ord) << 54) | (uint64_t(bin) << 42) | (uint64_t(th) << 32) | row;
+}
+constexpr uint32_t tl_sparse_key_ord(uint64_t k) { return uint32_t(k >> 54); }
+constexpr uint32_t tl_sparse_key_bin(uint64_t k) { return uint32_t(k >> 42) & 0xfff; }
+constexpr uint32_t tl_sparse_key_thread(uint64_t k) { return uint32_t(k >> 32) & 0x3ff; }
+constexpr uint32_t tl_sparse_key_row(uint64_t k) { return uint32_t(k); }
+// A full 64-bit mix for the table's start slot (the murmur3 finaliser): the
+// ordinal and the bin sit in the key's high bits, which sparse_slot's
+// multiplicative hash does not see.
+constexpr uint64_t tl_sparse_hash(uint64_t k) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+
+// The timeline's rows: the nd dense rows (entry, bin, thread, row, count), in
+// entry order, merged with the table's n (key, count) words, sorted by key and
+// decoded through sp_ids (ordinal -> entry), into out[(nd + n) * 5] -- one
+// list in (entry, bin, thread, row) order (an entry is dense or sparse, never
+// both).  out may hold the dense rows in its own tail (dense == out + n * 5):
+// the write position never passes the dense read position.
+inline void tl_merge_rows(const uint32_t* dense, uint64_t nd, const uint64_t* kv, uint64_t n,
+                          const std::vector<uint32_t>& sp_ids, uint32_t* out) {
+  uint64_t i = 0, j = 0;
+  uint32_t* w = out;
+  while (i < nd || j < n) {
+    const uint32_t es = j < n ? sp_ids[tl_sparse_key_ord(kv[2 * j])] : ~0u;
+    if (i < nd && (j == n || dense[5 * i] < es)) {
+      for (int k = 0; k < 5; k++) w[k] = dense[5 * i + k];
+      i++;
+    } else {
+      const uint64_t k = kv[2 * j];
+      w[0] = es;
+      w[1] = tl_sparse_key_bin(k);
+      w[2] = tl_sparse_key_thread(k);
+      w[3] = tl_sparse_key_row(k);
+      w[4] = (uint32_t)kv[2 * j + 1];
+      j++;
+    }
+    w += 5;
+  }
+}
+
 // ---- dump modes: what the report writer needs besides the counters
 struct DumpBuffer {
   const uint8_t* data;    // the linearised buffer

@@ -148,6 +148,13 @@ struct Params {
   uint64_t tl_t0;
   uint32_t tl_bin_shift, tl_nb_bins, tl_row_shift;
   uint32_t tl_rounds;  // timeline_add's merge rounds (kTlRounds)
+  // the timeline sparse table (nmg_set_timeline_ex, NMG_TL_SCOPE_ALL): the
+  // cells of the selected sparse entries, tl_sparse_key -> u32 count, open
+  // addressing over tls_mask + 1 slots (timeline_sparse_add); null unless a
+  // sparse entry is selected.  Such an entry's pad1 is tl_pad_sparse(ordinal).
+  uint64_t* tls_keys;
+  uint32_t* tls_vals;
+  uint32_t tls_mask;
   // page cost cells (nmg_set_page_cost): u64 cells at the page histogram's
   // index, thread * hist_cells + cell; null: off.  The rule is in
   // include/numamma_gpu.h (cost_selected / cost_add in nmg_device.h).
@@ -179,6 +186,12 @@ constexpr uint32_t kCostRounds = 4;
 // + (page >> row_shift), below 2^32.
 constexpr uint64_t kTlNone = ~0ull;
 constexpr uint64_t tl_pad(uint32_t base, uint32_t rows) { return (uint64_t(rows) << 32) | base; }
+// ... or, for a selected sparse entry (NMG_TL_SCOPE_ALL), a tagged word with
+// its ordinal in the timeline sparse table's keys: bit 63 set, which no dense
+// pad has (its rows field R <= 2^24), and not kTlNone (the low word is the
+// ordinal, at most kTlMaxSparse - 1).
+constexpr uint64_t tl_pad_sparse(uint32_t ord) { return (1ull << 63) | ord; }
+constexpr bool tl_pad_is_sparse(uint64_t pad) { return pad != kTlNone && (pad >> 63) != 0; }
 
 // merge rounds of timeline_add (nmg_device.h) before the remaining lanes add
 // their own cell: Params::tl_rounds, kTlRounds unless the environment variable

@@ -274,7 +274,7 @@ __device__ __forceinline__ void sub_stamp(SubTimer& st, int i) {
 // Process one decoded record (`valid` = it is a SAMPLE).  Every lane of the
 // wave calls this together (wave-level reductions inside); vmask / fmask are
 // the wave's SAMPLE and matched lanes.
-template <int MODE, bool TIMING, bool COST>
+template <int MODE, bool TIMING, int COST>
 __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAcc& acc, const Lookup& L, SubTimer& st,
                                                bool valid, bool shortrec, uint64_t ts, uint64_t addr,
                                                uint64_t w, uint64_t dsrc, uint32_t access,
@@ -369,11 +369,17 @@ __device__ __forceinline__ void process_sample(Params& p, WgCounters& wc, LaneAc
   if (p.tl) {
     const uint64_t pad = p.entries[e].pad1;
     const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
-    timeline_add(p, pad != kTlNone, timeline_cell(p, pad, ts, th, page), p.tl_rounds);
+    // (COST == 2: a selected sparse entry's cell goes to the timeline sparse
+    // table; in the other instances no entry has such a pad -- launch_attribute)
+    const bool tls = COST == 2 && tl_pad_is_sparse(pad);
+    timeline_add(p, pad != kTlNone && !tls, timeline_cell(p, pad, ts, th, page), p.tl_rounds);
+    if (COST == 2 && tls) timeline_sparse_add(p, timeline_sparse_key(p, pad, ts, th, page), in1 ? b1.seq : b0.seq, off);
   }
   // page cost cells: the histogram's cell of a selected sample (dense entries
-  // only).  COST: the instances for engines with cost cells set, so that the
-  // others are the code they were before the cells existed.
+  // only).  COST: 1 the instances for engines with cost cells set, 2 those for
+  // engines with a timeline sparse table (cost cells or not: the probe loop
+  // put 20 B of scratch into the mode 4 cost instance), so that
+  // the others are the code they were before either existed.
   if (COST && p.cost) {
     const uint32_t page = uint32_t(int(uint64_t(addr - m.baddr) / kPageSize));
     const uint64_t v = m.hist != kHistSparse ? cost_value(p, access, lvl, w) : 0ull;
@@ -526,7 +532,7 @@ __device__ __forceinline__ void load_slot(const Params& p, const WinLane& w, con
   load_rec(p.data + off, w.pos, len, r);
 }
 
-template <bool TIMING, int MODE, bool COST>
+template <bool TIMING, int MODE, int COST>
 __global__ __launch_bounds__(kWG, 1) void attribute_kernel(Params p) {
   __shared__ uint4 s_tab[kTabBytes / 16];  // lookup structure (layouts at kTabBytes)
   __shared__ uint32_t s_list[kMaxList];
@@ -1274,17 +1280,19 @@ hipError_t launch_attribute(bool timing, int mode, uint32_t grid, hipStream_t s,
 #define NMG_ATTR8(T, C)                                                                                      \
   {attribute_kernel<T, 0, C>, attribute_kernel<T, 1, C>, attribute_kernel<T, 2, C>, attribute_kernel<T, 3, C>, \
    attribute_kernel<T, 4, C>, attribute_kernel<T, 5, C>, attribute_kernel<T, 6, C>, attribute_kernel<T, 7, C>}
-  // [page cost cells set][timing][mode]
-  static const AttributeKernel k[2][2][8] = {{NMG_ATTR8(false, false), NMG_ATTR8(true, false)},
-                                             {NMG_ATTR8(false, true), NMG_ATTR8(true, true)}};
+  // [0: neither, 1: page cost cells set, 2: timeline sparse table set][timing][mode]
+  static const AttributeKernel k[3][2][8] = {{NMG_ATTR8(false, 0), NMG_ATTR8(true, 0)},
+                                             {NMG_ATTR8(false, 1), NMG_ATTR8(true, 1)},
+                                             {NMG_ATTR8(false, 2), NMG_ATTR8(true, 2)}};
 #undef NMG_ATTR8
-  hipLaunchKernelGGL(k[p.cost || p.sparse_cost ? 1 : 0][timing ? 1 : 0][mode & 7], dim3(grid), dim3(kWG), 0, s, p);
+  const int extra = p.tls_keys ? 2 : (p.cost || p.sparse_cost) ? 1 : 0;
+  hipLaunchKernelGGL(k[extra][timing ? 1 : 0][mode & 7], dim3(grid), dim3(kWG), 0, s, p);
   return hipGetLastError();
 }
 
 int attribute_blocks_per_cu() {
   int bpc = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (attribute_kernel<false, 0, false>), kWG, 0) != hipSuccess || bpc <= 0)
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (attribute_kernel<false, 0, 0>), kWG, 0) != hipSuccess || bpc <= 0)
     bpc = 1;
   return bpc;
 }

@@ -404,7 +404,30 @@ int timeline_prepare(nmg_engine* h) {
       HIP_TRY(h, hipStreamSynchronize(st));
     }
   }
-  t.rows.n = (int64_t)n;
+  t.nd = (int64_t)n;
+  // NMG_TL_SCOPE_ALL: the timeline sparse table's used slots, compacted on the
+  // device so that only they cross PCIe, sorted by key -- (entry, bin, thread,
+  // row) order -- and kept for timeline_fill
+  t.sp_kv.clear();
+  if (t.sp_cap) {
+    HIP_TRY(h, t.d_sp_ck.reserve(t.sp_cap));
+    HIP_TRY(h, t.d_sp_ck.compact(h->stream, t.d_sp_keys.get(), t.d_sp_vals.get()));
+    rc = t.d_sp_ck.download(h, t.sp_kv);
+    if (rc) return rc;
+    sparse_words_sort(t.sp_kv);
+  }
+  t.rows.n = t.nd + (int64_t)(t.sp_kv.size() / 2);
+  return NMG_OK;
+}
+
+// rows[s.n * 5]: the dense rows D2H into the tail, then merged with the sparse
+// table's rows from the front (tl_merge_rows: each at its entry's position)
+int timeline_fill(nmg_engine* h, const RowSet<uint32_t, 5>& s, uint32_t* rows) {
+  const Timeline& t = h->tl;
+  const uint64_t ns = t.sp_kv.size() / 2;
+  uint32_t* dense = rows + ns * 5;
+  if (t.nd) HIP_TRY(h, hipMemcpy(dense, s.d_rows, (size_t)t.nd * 5 * 4, hipMemcpyDeviceToHost));
+  if (ns) tl_merge_rows(dense, (uint64_t)t.nd, t.sp_kv.data(), ns, t.sp_ids, rows);
   return NMG_OK;
 }
 
@@ -415,7 +438,7 @@ extern "C" int64_t nmg_count_timeline_cells(nmg_engine* h) {
 
 extern "C" int nmg_get_timeline_cells(nmg_engine* h, uint32_t* rows, int64_t n) {
   if (!h || (n && !rows)) return NMG_ERR_INVALID;
-  return rows_get(h, h->tl.rows, timeline_prepare, rows, n);
+  return rows_get(h, h->tl.rows, timeline_prepare, rows, n, timeline_fill);
 }
 
 // ---- multi-GPU merge support

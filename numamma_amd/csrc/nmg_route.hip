@@ -154,7 +154,9 @@ __device__ __forceinline__ void direct_attribute(const Params& p, uint64_t addr,
   }
   if (TL && p.tl) {  // access timeline: this lane's own add (the callers' lanes are diverged; no merge here)
     const uint64_t pad = p.entries[e].pad1;
-    timeline_add(p, pad != kTlNone, timeline_cell(p, pad, ts, th, page), 0);
+    const bool tls = tl_pad_is_sparse(pad);  // a selected sparse entry: its cell is in the timeline sparse table
+    timeline_add(p, pad != kTlNone && !tls, timeline_cell(p, pad, ts, th, page), 0);
+    if (tls) timeline_sparse_add(p, timeline_sparse_key(p, pad, ts, th, page), seq, off);
   }
   if (TL && p.cost && m.hist != kHistSparse) {  // page cost cells: again the lane's own add
     const uint64_t v = cost_value(p, acc, lvl, w);
@@ -1801,8 +1803,15 @@ __global__ __launch_bounds__(kLWG, 1) void local_kernel(LocalParams lp) {
 #pragma unroll
             for (int j = 0; j < kLC; j++) {
               const uint64_t ft = xr[j].esc ? ts[j] : lp.xl.tbase + ts[j];
-              timeline_add(p, pad[j] != kTlNone,
-                           timeline_cell(p, pad[j], ft, xr[j].th, uint32_t(int(pofs[j] / kPageSize))), p.tl_rounds);
+              const uint32_t pg = uint32_t(int(pofs[j] / kPageSize));
+              const bool tls = tl_pad_is_sparse(pad[j]);
+              timeline_add(p, pad[j] != kTlNone && !tls, timeline_cell(p, pad[j], ft, xr[j].th, pg), p.tl_rounds);
+              // A selected sparse entry's cell (NMG_TL_SCOPE_ALL): outside the
+              // merge rounds above, the lane's own probe and add in the
+              // timeline sparse table.
+              if (tls)
+                timeline_sparse_add(p, timeline_sparse_key(p, pad[j], ft, xr[j].th, pg), lp.seq0 + xr[j].g(lp.xl),
+                                    xr[j].off(lp.xl));
             }
           }
           // The page cost cells (wave-uniform here too).  The entry's first

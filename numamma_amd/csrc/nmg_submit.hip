@@ -647,6 +647,12 @@ Params base_params(nmg_engine* h, const uint8_t* data, const BufDesc* sdescs, co
     p.tl_nb_bins = h->tl.opt.nb_bins;
     p.tl_row_shift = h->tl.opt.row_shift;
     p.tl_rounds = h->tl.rounds;
+    if (h->tl.sp_cap) {  // NMG_TL_SCOPE_ALL with a sparse entry selected
+      p.tls_keys = h->tl.d_sp_keys;
+      p.tls_vals = h->tl.d_sp_vals;
+      p.tls_mask = (uint32_t)(h->tl.sp_cap - 1);
+      h->tl.sp_touched = true;  // (these parameters are for a launch: the next reset clears the table)
+    }
   }
   if (h->cost.on) {
     p.cost = h->cost.d_cells;  // (null while the table has no dense cell: nothing to count)

@@ -170,8 +170,19 @@ extern "C" int nmg_set_objects(nmg_engine* h, const uint64_t* keys, const uint32
 // records) carry pad1 too but nothing reads it there, so a later accepted
 // update -- it rebuilds those from the host records -- keeps the bases.
 extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
+  return nmg_set_timeline_ex(h, o, NMG_TL_SCOPE_DENSE);
+}
+
+// scope NMG_TL_SCOPE_ALL: the sparse entries of at least min_object_bytes are
+// selected too.  They get no block: each gets an ordinal, in id order, into
+// its pad1 (tl_pad_sparse), and their non-zero cells live in the timeline
+// sparse table (Timeline::d_sp_keys / d_sp_vals), sparse_capacity slots of 12
+// bytes within the same budget, allocated only when there is such an entry.
+extern "C" int nmg_set_timeline_ex(nmg_engine* h, const nmg_timeline_options* o, uint32_t scope) {
   if (!h) return NMG_ERR_INVALID;
   h->epoch++;
+  if (scope > NMG_TL_SCOPE_ALL)
+    return fail(h, NMG_ERR_INVALID, "nmg_set_timeline_ex: scope is NMG_TL_SCOPE_DENSE or NMG_TL_SCOPE_ALL");
   if (h->multi || !h->workers.empty()) return fail(h, NMG_ERR_INVALID, "nmg_set_timeline: not on a multi-GPU handle");
   constexpr uint32_t kNeed = NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST;
   if ((h->flags & kNeed) != kNeed)
@@ -193,11 +204,17 @@ extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
   const uint32_t E = h->E, T = h->T;
   Timeline t;
   t.opt = *o;
+  t.scope = scope;
   if (const char* r = getenv("NMG_TL_ROUNDS")) t.rounds = (uint32_t)std::min(64, std::max(0, atoi(r)));  // (see kTlRounds)
   const uint64_t budget = o->budget_bytes ? o->budget_bytes : (1ull << 30);
   unsigned __int128 need = 0;
+  uint64_t nsparse = 0;  // selected sparse entries (past kTlMaxSparse refused below: only counted)
   for (uint32_t e = 0; e < E; e++) {
-    if (tab.hist_base[e] == kHistSparse || tab.buffer_size[e] < o->min_object_bytes) continue;
+    if (tab.buffer_size[e] < o->min_object_bytes) continue;
+    if (tab.hist_base[e] == kHistSparse) {
+      if (scope == NMG_TL_SCOPE_ALL && nsparse++ < kTlMaxSparse) t.sp_ids.push_back(e);
+      continue;
+    }
     const uint64_t R = (tab.buffer_size[e] / kPageSize + 1 + (1ull << o->row_shift) - 1) >> o->row_shift;
     if (need <= 0xffffffffull) {  // (past it the layout is refused below: only the size is still summed)
       t.ids.push_back(e);
@@ -206,11 +223,24 @@ extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
     }
     need += (unsigned __int128)R * o->nb_bins * T;
   }
-  const unsigned __int128 bytes = need * 4;
+  if (nsparse > kTlMaxSparse) {
+    char msg[224];
+    snprintf(msg, sizeof(msg), "nmg_set_timeline_ex: %llu sparse entries selected, at most %u (raise min_object_bytes, "
+                               "or the engine's hist_budget_bytes so that fewer entries are sparse)",
+             (unsigned long long)nsparse, kTlMaxSparse);
+    return fail(h, NMG_ERR_CAPACITY, msg);
+  }
+  t.sp_cap = t.sp_ids.empty() ? 0 : h->sparse_cap;
+  const unsigned __int128 bytes = need * 4 + (unsigned __int128)t.sp_cap * 12;
   if (need > 0xffffffffull || bytes > budget) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "nmg_set_timeline: the cells need %llu bytes (budget %llu, at most 2^32 - 1 cells)",
-             bytes > ~0ull ? ~0ull : (unsigned long long)bytes, (unsigned long long)budget);
+    char msg[224];
+    if (t.sp_cap)
+      snprintf(msg, sizeof(msg), "nmg_set_timeline_ex: the cells and the sparse table (%llu slots of 12 bytes) need %llu "
+                                 "bytes (budget %llu, at most 2^32 - 1 cells)",
+               (unsigned long long)t.sp_cap, bytes > ~0ull ? ~0ull : (unsigned long long)bytes, (unsigned long long)budget);
+    else
+      snprintf(msg, sizeof(msg), "nmg_set_timeline: the cells need %llu bytes (budget %llu, at most 2^32 - 1 cells)",
+               bytes > ~0ull ? ~0ull : (unsigned long long)bytes, (unsigned long long)budget);
     return fail(h, NMG_ERR_CAPACITY, msg);
   }
   t.ncells = (uint64_t)need;
@@ -219,11 +249,20 @@ extern "C" int nmg_set_timeline(nmg_engine* h, const nmg_timeline_options* o) {
   std::vector<DevEntry> dev = tab.dev_entries;
   for (DevEntry& d : dev) d.pad1 = kTlNone;
   for (size_t k = 0; k < t.ids.size(); k++) dev[t.ids[k]].pad1 = tl_pad(t.base[k], t.nrows[k]);
+  for (size_t k = 0; k < t.sp_ids.size(); k++) dev[t.sp_ids[k]].pad1 = tl_pad_sparse((uint32_t)k);
+  // (Params::tl switches the kernels' timeline code on; it is never null,
+  // with sparse entries alone selected either: DevBuf::alloc(0))
   HIP_TRY(h, t.d_cells.alloc(t.ncells));
   HIP_TRY(h, hipMemsetAsync(t.d_cells, 0, t.ncells * 4, h->stream));
   HIP_TRY(h, alloc_copy(h, t.d_ids, t.ids));
   HIP_TRY(h, alloc_copy(h, t.d_base, t.base));
   HIP_TRY(h, alloc_copy(h, t.d_nrows, t.nrows));
+  if (t.sp_cap) {
+    HIP_TRY(h, t.d_sp_keys.alloc(t.sp_cap));
+    HIP_TRY(h, t.d_sp_vals.alloc(t.sp_cap));
+    HIP_TRY(h, hipMemsetAsync(t.d_sp_keys, 0xff, t.sp_cap * 8, h->stream));
+    HIP_TRY(h, hipMemsetAsync(t.d_sp_vals, 0, t.sp_cap * 4, h->stream));
+  }
   if (E) HIP_TRY(h, hipMemcpyAsync(h->d_entries, dev.data(), (size_t)E * sizeof(DevEntry), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // (pageable sources)
   tab.dev_entries = std::move(dev);

@@ -336,15 +336,20 @@ class Engine:
 
     # ---- access timeline
     def set_timeline(self, t0: Optional[int] = 0, bin_shift: int = 0, nb_bins: int = 1, row_shift: int = 0,
-                     min_object_bytes: int = 0, budget_bytes: int = 0, reserved: int = 0):
+                     min_object_bytes: int = 0, budget_bytes: int = 0, reserved: int = 0,
+                     scope: int = _lib.NMG_TL_SCOPE_DENSE):
         """nmg_set_timeline: u32 counters [time bin][thread][row] per selected
         object, counted by every analysis from now on.  set_timeline(None)
-        drops the timeline."""
-        if t0 is None:
-            self._c(lib.nmg_set_timeline(self.h, None))
-            return
-        o = _lib.nmg_timeline_options(t0, bin_shift, nb_bins, row_shift, reserved, min_object_bytes, budget_bytes)
-        self._c(lib.nmg_set_timeline(self.h, C.byref(o)))
+        drops the timeline.  scope = NMG_TL_SCOPE_ALL (nmg_set_timeline_ex):
+        the objects with sparse page cells ([stack], arrays past the dense cap
+        or the histogram budget) are selected too, their non-zero cells kept in
+        a hashed table of the engine's sparse_capacity slots."""
+        o = None if t0 is None else C.byref(
+            _lib.nmg_timeline_options(t0, bin_shift, nb_bins, row_shift, reserved, min_object_bytes, budget_bytes))
+        if scope != _lib.NMG_TL_SCOPE_DENSE:
+            self._c(lib.nmg_set_timeline_ex(self.h, o, scope))
+        else:
+            self._c(lib.nmg_set_timeline(self.h, o))
 
     def timeline_cells(self) -> np.ndarray:
         """The non-zero timeline cells as (entry, bin, thread, row, count) rows,

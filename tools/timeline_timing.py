@@ -17,8 +17,12 @@ one box by construction:
              record of a hot object and thread on one word
 The timeline: min_object_bytes 4096, row_shift 0, 64 bins of 2^28 ns from the
 generator's first timestamp on (its 10 s horizon ends in bin 37).
-NMG_LIB_PATH picks another build of the library; one that predates the
-timeline runs `plain` and `levels` only (--no-timeline)."""
+--scope all sets it with NMG_TL_SCOPE_ALL (nmg_set_timeline_ex): at the
+configs[3] shard no record matches a sparse entry, so the difference to the
+dense scope is the price of the kernels' checks alone.
+NMG_LIB_PATH picks another build of the library (with NMG_LIB_AB=1 an older
+one); one that predates the timeline runs `plain` and `levels` only
+(--no-timeline), one that predates the scope the dense scope only."""
 import argparse
 import json
 import os
@@ -39,6 +43,9 @@ def main():
     ap.add_argument("--one-cell", action="store_true",
                     help="also time a timeline of one bin and one row per object (the hottest cells the data can give)")
     ap.add_argument("--no-timeline", action="store_true", help="the yardsticks only (a library without the timeline)")
+    ap.add_argument("--scope", choices=["dense", "all"], default="dense",
+                    help="all: NMG_TL_SCOPE_ALL (nmg_set_timeline_ex) -- the sparse entries selected too, their cells in "
+                         "the timeline sparse table; needs a library that has it")
     args = ap.parse_args()
     if not 1 <= args.steps <= 64:
         ap.error("--steps: 1 to 64 (the engine keeps the events of its last 64 launches)")
@@ -82,7 +89,7 @@ def main():
         return eng
 
     out = {"tool": "timeline_timing", "workload": args.workload, "records": w.samples, "steps": args.steps,
-           "warmup": args.warmup, "library": os.path.relpath(_lib.LIB_PATH, ROOT), "variants": {}}
+           "warmup": args.warmup, "scope": args.scope, "library": os.path.relpath(_lib.LIB_PATH, ROOT), "variants": {}}
     out["variants"]["plain"] = timed(w.eng)
     w.eng.close()
     eng = engine(_lib.NMG_F_DEFAULT | _lib.NMG_F_OBJECT_LEVELS)
@@ -97,7 +104,10 @@ def main():
             for r in [int(x) for x in args.rounds.split(",")]:
                 os.environ["NMG_TL_ROUNDS"] = str(r)  # (read when the timeline is set)
                 eng = engine(_lib.NMG_F_DEFAULT)
-                eng.set_timeline(**tl)
+                if args.scope == "all":
+                    eng.set_timeline(**tl, scope=_lib.NMG_TL_SCOPE_ALL)
+                else:
+                    eng.set_timeline(**tl)
                 res = timed(eng)
                 rows = eng.timeline_cells()
                 mul = np.array([3, 5, 7, 11, 13], dtype="uint64")
