@@ -387,8 +387,10 @@ int nmg_set_timeline(nmg_engine *h, const struct nmg_timeline_options *tl);
  * nmg_set_timeline(h, NULL) or a later nmg_set_objects drops it, and
  * nmg_update_objects keeps its rule, so no entry changes kind under it.  Like
  * the dense cells, the table is not carried by the results snapshot
- * (nmg_results_begin), nmg_sparse_import, the multi-GPU merge or
- * nmg_run_replay.  The getters return dense and sparse entries' rows in one
+ * (nmg_results_begin), nmg_sparse_import, the in-process multi-GPU handle or
+ * nmg_run_replay; the one-process-per-GPU merge carries both: the dense cells
+ * as NMG_ARR_TL32 (or nmg_cells_pack), the table through nmg_sparse_export_ex /
+ * nmg_sparse_import_ex with NMG_SPARSE_TIMELINE (below).  The getters return dense and sparse entries' rows in one
  * list sorted by (entry, bin, thread, row), non-zero counts only;
  * nmg_report_timeline gives a site its sparse members' cells too (stack sites
  * have no file, as in nmg_report_page_cost). */
@@ -457,8 +459,10 @@ int nmg_get_timeline_cells(nmg_engine *h, uint32_t *rows /* [n][5] */, int64_t n
  * a count but no selected sample gives no row.  An entry that an online
  * update turned from sparse to dense loses its sparse rows, as it loses its
  * sparse page cells.  nmg_reset_counters zeroes the sparse cost cells with
- * the sparse table; nmg_sparse_import rebuilds that table, so it zeroes them
- * too: cost cells, dense or sparse, are not merged across ranks.  The
+ * the sparse table; nmg_sparse_import rebuilds that table, so it still zeroes
+ * them, and the caller follows it with the cost import
+ * (nmg_sparse_import_ex with NMG_SPARSE_PAGE_COST, below).  Across ranks the
+ * dense cells merge as NMG_ARR_COST64 (or nmg_cells_pack).  The
  * placement folds the cells that exist (source NMG_PLACE_PAGE_COST, below),
  * and nmg_report_page_cost gives a site its sparse members' cells too (stack
  * sites stay skipped). */
@@ -513,12 +517,26 @@ int nmg_results_end(nmg_engine *h, struct nmg_results_view *out);
  *   NMG_ARR_MIN64  : u64 mins   (global bucket mins, first-match ordinals, error word)
  *   NMG_ARR_MAX64  : u64 maxes  (global bucket maxes)
  *   NMG_ARR_HIST32 : u32 sums   (dense page histogram)
+ *   NMG_ARR_COST64 : u64 sums   (dense page cost cells, at the histogram's own
+ *                                index: nmg_array_size(HIST32) cells while cost
+ *                                cells are set, 0 otherwise)
+ *   NMG_ARR_TL32   : u32 sums   (dense timeline cells: every selected dense
+ *                                entry's [bin][thread][row] block while a
+ *                                timeline is set, 0 otherwise)
+ * The in-process multi-GPU handle (nmg_options.nb_gpus > 1) merges the first
+ * four only: it refuses nmg_set_timeline and nmg_set_page_cost.
+ * The merge's precondition: the cells of the two last arrays, and the keys of
+ * the three sparse kinds below, are equal across engines that were given the
+ * same table, nb_threads, hist_budget_bytes and product options
+ * (nmg_set_timeline_ex, nmg_set_page_cost_ex, scope included).
  * nmg_export_array copies device -> device (dst is a device pointer),
  * nmg_import_array copies back.  Sizes in elements. */
 #define NMG_ARR_SUM64 0
 #define NMG_ARR_MIN64 1
 #define NMG_ARR_MAX64 2
 #define NMG_ARR_HIST32 3
+#define NMG_ARR_COST64 4
+#define NMG_ARR_TL32 5
 uint64_t nmg_array_size(nmg_engine *h, int which);
 int nmg_export_array(nmg_engine *h, int which, void *d_dst);
 int nmg_import_array(nmg_engine *h, int which, const void *d_src);
@@ -534,6 +552,20 @@ int nmg_import_array(nmg_engine *h, int which, const void *d_src);
  * padding): histogram = bytes + overflow, exactly the u32 sum. */
 int nmg_hist_pack(nmg_engine *h, uint32_t threshold, void *d_u8, void *d_ovf, uint64_t ovf_cap, uint64_t *n_ovf);
 int nmg_hist_unpack(nmg_engine *h, const void *d_u8, const void *d_ovf, uint64_t n_ovf);
+/* The page cost cells or the timeline cells packed for the merge: both arrays
+ * are almost entirely zero, so the payload is their non-zero cells, compacted
+ * on the device.
+ * which: NMG_ARR_COST64 or NMG_ARR_TL32.  The array's non-zero cells as (cell index, value) u64 pairs,
+ * 16 bytes each, in ascending cell order, to d_list (device, cap pairs).  *n = their number; when
+ * *n > cap the list is incomplete and nothing past cap pairs is written: merge the array itself. */
+int nmg_cells_pack(nmg_engine *h, int which, void *d_list, uint64_t cap, uint64_t *n);
+/* array[index] += value for each of the n pairs.  Pairs with value 0 are padding.  The same index may
+ * occur any number of times (the lists of several ranks back to back).  An index outside the array is
+ * NMG_ERR_RANGE, as in nmg_hist_unpack.  Ends the results epoch.
+ * Both: NMG_ERR_INVALID before a table exists, for any other `which`, and for a
+ * null list with a non-zero cap or n; NMG_OK with *n = 0, nothing added, while
+ * the array is empty. */
+int nmg_cells_unpack_add(nmg_engine *h, int which, const void *d_list, uint64_t n);
 /* Packed per-object counters for the merge: the count and
  * weight rows of a sum64 image (nmg_export_array(NMG_ARR_SUM64) into d_sum64)
  * as u32 words where a value is below `threshold` (2^32 / ranks: the sum over
@@ -550,6 +582,26 @@ int nmg_objcw_unpack(nmg_engine *h, void *d_sum64, const void *d_u32, const void
 int64_t nmg_sparse_count(nmg_engine *h);
 int nmg_sparse_export(nmg_engine *h, uint64_t *keys, uint32_t *counts, int64_t n);
 int nmg_sparse_import(nmg_engine *h, const uint64_t *keys, const uint32_t *counts, int64_t n);
+/* The sparse parts by kind, values as u64: the used slots with a non-zero
+ * value, in ascending key order (keys are unique).
+ *   NMG_SPARSE_PAGE_COUNTS: the three functions above (import: a value of 2^32
+ *     or more is NMG_ERR_RANGE).
+ *   NMG_SPARSE_PAGE_COST: the sparse cost cells.  Import zeroes all of them,
+ *     then stores each value at its key's slot of the sparse page table: call
+ *     it after nmg_sparse_import.  A key absent from that table is
+ *     NMG_ERR_INVALID (the detail names their number) and leaves the cells
+ *     zeroed; n > 0 on an engine without sparse cost cells is NMG_ERR_STATE.
+ *   NMG_SPARSE_TIMELINE: the timeline sparse table.  Import clears it and
+ *     inserts the pairs; the next nmg_reset_counters clears it again.
+ *     n above the table's slots is NMG_ERR_CAPACITY, a value of 2^32 or more
+ *     NMG_ERR_RANGE, n > 0 without such a table NMG_ERR_STATE.
+ * Any other kind is NMG_ERR_INVALID.  Every import ends the results epoch. */
+#define NMG_SPARSE_PAGE_COUNTS 0 /* the sparse page table: nmg_sparse_count / _export / _import themselves */
+#define NMG_SPARSE_PAGE_COST 1   /* the sparse cost cells (NMG_COST_SCOPE_ALL): key = the page table's key */
+#define NMG_SPARSE_TIMELINE 2    /* the timeline sparse table (NMG_TL_SCOPE_ALL): key = (ordinal, bin, thread, row) */
+int64_t nmg_sparse_count_ex(nmg_engine *h, uint32_t which);
+int nmg_sparse_export_ex(nmg_engine *h, uint32_t which, uint64_t *keys, uint64_t *vals, int64_t n);
+int nmg_sparse_import_ex(nmg_engine *h, uint32_t which, const uint64_t *keys, const uint64_t *vals, int64_t n);
 /* replace per-buffer counts with the whole job's (rank 0 before reporting) */
 int nmg_set_buffer_counts(nmg_engine *h, uint32_t nb_buffers, const uint32_t *nb_samples,
                           const uint32_t *nb_found, const uint64_t *buffer_bytes);

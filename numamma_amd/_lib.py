@@ -46,6 +46,8 @@ NMG_F_ALL = NMG_F_MATCH_SAMPLES | NMG_F_PAGE_HIST | NMG_F_OBJECT_LEVELS | NMG_F_
 NMG_OPTIONS_V1_SIZE = 32
 NMG_DUMP_CALLSITES, NMG_DUMP_ALL, NMG_DUMP_UNMATCHED = 0x1, 0x2, 0x4
 NMG_ARR_SUM64, NMG_ARR_MIN64, NMG_ARR_MAX64, NMG_ARR_HIST32 = range(4)
+NMG_ARR_COST64, NMG_ARR_TL32 = 4, 5  # the dense page cost cells (u64) and timeline cells (u32)
+NMG_SPARSE_PAGE_COUNTS, NMG_SPARSE_PAGE_COST, NMG_SPARSE_TIMELINE = range(3)  # nmg_sparse_*_ex kinds
 ERRORS = {
     -1: "NMG_ERR_INVALID",
     -2: "NMG_ERR_HIP",
@@ -274,11 +276,16 @@ _SIGS = {
     "nmg_import_array": (C.c_int, [H, C.c_int, P]),
     "nmg_hist_pack": (C.c_int, [H, C.c_uint32, P, P, C.c_uint64, u64p]),
     "nmg_hist_unpack": (C.c_int, [H, P, P, C.c_uint64]),
+    "nmg_cells_pack": (C.c_int, [H, C.c_int, P, C.c_uint64, u64p]),
+    "nmg_cells_unpack_add": (C.c_int, [H, C.c_int, P, C.c_uint64]),
     "nmg_objcw_pack": (C.c_int, [H, P, C.c_uint64, P, P, C.c_uint64, u64p]),
     "nmg_objcw_unpack": (C.c_int, [H, P, P, P, C.c_uint64]),
     "nmg_sparse_count": (C.c_int64, [H]),
     "nmg_sparse_export": (C.c_int, [H, u64p, u32p, C.c_int64]),
     "nmg_sparse_import": (C.c_int, [H, u64p, u32p, C.c_int64]),
+    "nmg_sparse_count_ex": (C.c_int64, [H, C.c_uint32]),
+    "nmg_sparse_export_ex": (C.c_int, [H, C.c_uint32, u64p, u64p, C.c_int64]),
+    "nmg_sparse_import_ex": (C.c_int, [H, C.c_uint32, u64p, u64p, C.c_int64]),
     "nmg_set_buffer_counts": (C.c_int, [H, C.c_uint32, u32p, u32p, u64p]),
     "nmg_last_analyze_ms": (C.c_int, [H, C.POINTER(C.c_float)]),
     "nmg_get_merge_stats": (C.c_int, [H, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),

@@ -251,6 +251,22 @@ hipError_t launch_sparse_compact(hipStream_t s, const uint64_t* keys, const uint
                                  uint64_t* out, unsigned long long* cnt);
 hipError_t launch_sparse_insert(hipStream_t s, uint64_t* keys, uint32_t* vals, uint64_t cap, const uint64_t* pairs,
                                 uint64_t n);
+// the same into the timeline sparse table (tl_sparse_hash)
+hipError_t launch_tl_sparse_insert(hipStream_t s, uint64_t* keys, uint32_t* vals, uint64_t cap, const uint64_t* pairs,
+                                   uint64_t n);
+// the sparse cost cells' import: cost[slot of key] = value per pair, the keys absent from the page table into *bad
+hipError_t launch_sparse_cost_store(hipStream_t s, const uint64_t* keys, uint64_t* cost, uint64_t cap,
+                                    const uint64_t* pairs, uint64_t n, unsigned long long* bad);
+// packed cells (nmg_cells_pack / nmg_cells_unpack_add): the non-zero cells of the timeline (u32) or the page cost
+// (u64) array as 16 B (cell index, value) pairs in cell order, *cnt of them, at most cap written
+hipError_t launch_cells_pack(hipStream_t s, const uint32_t* cells, uint64_t ncells, void* list, uint64_t cap,
+                             unsigned long long* cnt, uint32_t* wgcnt);  // wgcnt: [1024] workspace
+hipError_t launch_cells_pack(hipStream_t s, const uint64_t* cells, uint64_t ncells, void* list, uint64_t cap,
+                             unsigned long long* cnt, uint32_t* wgcnt);
+hipError_t launch_cells_add(hipStream_t s, uint32_t* cells, uint64_t ncells, const void* list, uint64_t n,
+                            unsigned long long* bad);
+hipError_t launch_cells_add(hipStream_t s, uint64_t* cells, uint64_t ncells, const void* list, uint64_t n,
+                            unsigned long long* bad);
 hipError_t launch_hist_pack(hipStream_t s, const uint32_t* hist, uint64_t ncells, uint32_t thr, void* u8, void* ovf,
                             uint64_t cap, unsigned long long* cnt, uint32_t* wgcnt);  // wgcnt: [1024] workspace
 hipError_t launch_hist_unpack(hipStream_t s, uint32_t* hist, uint64_t ncells, const void* u8, const void* ovf,

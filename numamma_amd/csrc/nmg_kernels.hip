@@ -1250,15 +1250,26 @@ __global__ __launch_bounds__(256) void sparse_compact_kernel(const uint64_t* key
   }
 }
 
-// nmg_sparse_import: (key, count) pairs into a cleared table, with
-// sparse_add's hash and linear probing (n <= cap: every probe sequence ends)
+// The start slot of a key: the sparse page table's (sparse_slot) and the
+// timeline sparse table's (timeline_sparse_add)
+struct PageHash {
+  __device__ static uint64_t slot(uint64_t key) { return (key * 0x9E3779B97F4A7C15ull) >> 20; }
+};
+struct TimelineHash {
+  __device__ static uint64_t slot(uint64_t key) { return tl_sparse_hash(key); }
+};
+
+// nmg_sparse_import and the timeline table's import: (key, count) pairs into a
+// cleared table, with the table's own hash and linear probing (n <= cap: every
+// probe sequence ends)
+template <class HASH>
 __global__ __launch_bounds__(256) void sparse_insert_kernel(uint64_t* keys, uint32_t* vals, uint64_t mask,
                                                             const uint64_t* pairs, uint64_t n) {
   const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
   for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
     const uint64_t key = pairs[2 * i];
     const uint32_t cnt = (uint32_t)pairs[2 * i + 1];
-    uint64_t slot = ((key * 0x9E3779B97F4A7C15ull) >> 20) & mask;
+    uint64_t slot = HASH::slot(key) & mask;
     for (uint64_t probe = 0; probe <= mask; probe++) {
       const unsigned long long prev =
           atomicCAS(reinterpret_cast<unsigned long long*>(keys + slot), ~0ull, (unsigned long long)key);
@@ -1268,6 +1279,163 @@ __global__ __launch_bounds__(256) void sparse_insert_kernel(uint64_t* keys, uint
       }
       slot = (slot + 1) & mask;
     }
+  }
+}
+
+// The sparse cost cells' import: each pair's cost stored at the slot the sparse
+// page table gave its key (sparse_slot's hash and probing, reading only: the
+// table was built before this launch).  A probe that meets an empty slot, or
+// none of the key's after every slot, found the key absent: counted into *bad.
+__global__ __launch_bounds__(256) void sparse_cost_store_kernel(const uint64_t* keys, uint64_t* cost, uint64_t mask,
+                                                                const uint64_t* pairs, uint64_t n,
+                                                                unsigned long long* bad) {
+  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+  for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint64_t key = pairs[2 * i];
+    uint64_t slot = PageHash::slot(key) & mask;
+    bool found = false;
+    for (uint64_t probe = 0; probe <= mask && key != ~0ull; probe++) {
+      const uint64_t k = keys[slot];
+      found = k == key;
+      if (found || k == ~0ull) break;
+      slot = (slot + 1) & mask;
+    }
+    if (found) cost[slot] = pairs[2 * i + 1];  // (keys are unique: one writer per slot)
+    else atomicAdd(bad, 1ull);
+  }
+}
+
+// Packed cells for the multi-GPU merge (nmg_cells_pack): the non-zero cells of
+// a u32 or u64 array as (cell index, value) u64 pairs in cell order.  The two
+// passes of the packed histogram above -- contiguous per-workgroup ranges, a
+// count per range, then each range's first pair from the earlier ranges'
+// counts; no shared reservation counter -- over groups of 16 bytes: four u32
+// or two u64 cells per load, one 16 B store per pair.
+template <class CELL>
+struct CellGroup {
+  static constexpr uint32_t kCells = 16 / sizeof(CELL);
+  uint64_t c[kCells];
+  // cells kCells * i ..; those past n read as 0, the last, partial group by single loads
+  __device__ __forceinline__ void load(const CELL* a, uint64_t i, uint64_t n) {
+    if (kCells * i + (kCells - 1) < n) {
+      const uint4 v = reinterpret_cast<const uint4*>(a)[i];
+      if constexpr (kCells == 4) {
+        c[0] = v.x, c[1] = v.y, c[2] = v.z, c[3] = v.w;
+      } else {
+        c[0] = (uint64_t(v.y) << 32) | v.x;
+        c[1] = (uint64_t(v.w) << 32) | v.z;
+      }
+    } else {
+#pragma unroll
+      for (uint32_t k = 0; k < kCells; k++) c[k] = kCells * i + k < n ? (uint64_t)a[kCells * i + k] : 0ull;
+    }
+  }
+  __device__ __forceinline__ uint32_t nonzero() const {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kCells; k++) m += c[k] != 0;
+    return m;
+  }
+};
+
+template <class CELL>
+__global__ __launch_bounds__(kPackWG) void cells_count_nz_kernel(const CELL* cells, uint64_t ncells, uint32_t* wgcnt) {
+  using G = CellGroup<CELL>;
+  const uint64_t ng = (ncells + G::kCells - 1) / G::kCells;
+  __shared__ uint32_t s_sum[kPackWG / 64];
+  const uint64_t per = (ng + kPackGrid - 1) / kPackGrid, i0 = uint64_t(blockIdx.x) * per;
+  const uint64_t i1 = min(i0 + per, ng);
+  uint32_t nz = 0;
+  for (uint64_t i = i0 + threadIdx.x; i < i1; i += kPackWG) {
+    G g;
+    g.load(cells, i, ncells);
+    nz += g.nonzero();
+  }
+  nz = wave_sum_u32(nz);
+  if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = nz;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (uint32_t w = 0; w < kPackWG / 64; w++) t += s_sum[w];
+    wgcnt[blockIdx.x] = t;
+  }
+}
+
+template <class CELL>
+__global__ __launch_bounds__(kPackWG) void cells_pack_kernel(const CELL* cells, uint64_t ncells, uint4* list,
+                                                             uint64_t cap, const uint32_t* wgcnt,
+                                                             unsigned long long* cnt) {
+  using G = CellGroup<CELL>;
+  const uint64_t ng = (ncells + G::kCells - 1) / G::kCells;
+  __shared__ uint32_t s_w[kPackWG / 64];
+  __shared__ unsigned long long s_base;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint64_t per = (ng + kPackGrid - 1) / kPackGrid, i0 = uint64_t(blockIdx.x) * per;
+  const uint64_t i1 = min(i0 + per, ng);
+  // this range's first pair: the earlier ranges' counts (each below 2^32; their sum in 64 bits)
+  uint32_t pre_lo = 0, pre_hi = 0;
+  for (uint32_t w = tid; w < blockIdx.x; w += kPackWG) {
+    const uint32_t c = wgcnt[w];
+    pre_lo += c & 0xffffu;
+    pre_hi += c >> 16;
+  }
+  pre_lo = wave_sum_u32(pre_lo);
+  pre_hi = wave_sum_u32(pre_hi);
+  __shared__ unsigned long long s_pre[kPackWG / 64];
+  if (lane == 0) s_pre[wave] = (unsigned long long)pre_lo + ((unsigned long long)pre_hi << 16);
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long t = 0;
+    for (uint32_t w = 0; w < kPackWG / 64; w++) t += s_pre[w];
+    s_base = t;
+    if (blockIdx.x == gridDim.x - 1) *cnt = t + wgcnt[blockIdx.x];  // (the list's length)
+  }
+  __syncthreads();
+  unsigned long long base = s_base;
+  for (uint64_t j = i0; j < i1; j += kPackWG) {  // (uniform trip count: the scans below are workgroup-wide)
+    const uint64_t i = j + tid;
+    G g;
+    if (i < i1) g.load(cells, i, ncells);
+    const uint32_t nz = i < i1 ? g.nonzero() : 0u;
+    // workgroup-wide exclusive scan of nz (cell order)
+    const uint32_t inc = wave_incl_scan_u32(nz);
+    __syncthreads();  // (s_w of the previous iteration read by every wave)
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t wpre = 0, tot = 0;
+    for (int w = 0; w < kPackWG / 64; w++) {
+      wpre += w < wave ? s_w[w] : 0u;
+      tot += s_w[w];
+    }
+    uint64_t slot = base + wpre + inc - nz;
+    if (nz) {
+#pragma unroll
+      for (uint32_t k = 0; k < G::kCells; k++) {
+        if (!g.c[k]) continue;
+        const uint64_t cell = G::kCells * i + k;
+        if (slot < cap)
+          list[slot] = make_uint4((uint32_t)cell, (uint32_t)(cell >> 32), (uint32_t)g.c[k], (uint32_t)(g.c[k] >> 32));
+        slot++;
+      }
+    }
+    base += tot;
+  }
+}
+
+// nmg_cells_unpack_add: cells[index] += value per pair (one 16 B load each), a
+// device atomic because an index may repeat (several ranks' lists back to
+// back); value 0 is padding; an index outside the array is counted into *bad
+template <class CELL>
+__global__ __launch_bounds__(256) void cells_add_kernel(CELL* cells, uint64_t ncells, const uint4* list, uint64_t n,
+                                                        unsigned long long* bad) {
+  const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+  for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint4 e = list[i];
+    const uint64_t cell = (uint64_t(e.y) << 32) | e.x, v = (uint64_t(e.w) << 32) | e.z;
+    if (!v) continue;  // (padding)
+    if (cell >= ncells) atomicAdd(bad, 1ull);
+    else if (sizeof(CELL) == 4) atomicAdd(reinterpret_cast<uint32_t*>(cells) + cell, (uint32_t)v);
+    else atomicAdd(reinterpret_cast<unsigned long long*>(cells) + cell, (unsigned long long)v);
   }
 }
 
@@ -1638,8 +1806,59 @@ hipError_t launch_sparse_insert(hipStream_t s, uint64_t* keys, uint32_t* vals, u
                                 uint64_t n) {
   if (!n) return hipSuccess;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(sparse_insert_kernel, dim3(grid), dim3(256), 0, s, keys, vals, cap - 1, pairs, n);
+  hipLaunchKernelGGL(sparse_insert_kernel<PageHash>, dim3(grid), dim3(256), 0, s, keys, vals, cap - 1, pairs, n);
   return hipGetLastError();
+}
+
+hipError_t launch_tl_sparse_insert(hipStream_t s, uint64_t* keys, uint32_t* vals, uint64_t cap, const uint64_t* pairs,
+                                   uint64_t n) {
+  if (!n) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(sparse_insert_kernel<TimelineHash>, dim3(grid), dim3(256), 0, s, keys, vals, cap - 1, pairs, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_cost_store(hipStream_t s, const uint64_t* keys, uint64_t* cost, uint64_t cap,
+                                    const uint64_t* pairs, uint64_t n, unsigned long long* bad) {
+  if (!n) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(sparse_cost_store_kernel, dim3(grid), dim3(256), 0, s, keys, cost, cap - 1, pairs, n, bad);
+  return hipGetLastError();
+}
+
+template <class CELL>
+static hipError_t cells_pack(hipStream_t s, const CELL* cells, uint64_t ncells, void* list, uint64_t cap,
+                             unsigned long long* cnt, uint32_t* wgcnt) {
+  hipLaunchKernelGGL(cells_count_nz_kernel<CELL>, dim3(kPackGrid), dim3(kPackWG), 0, s, cells, ncells, wgcnt);
+  hipLaunchKernelGGL(cells_pack_kernel<CELL>, dim3(kPackGrid), dim3(kPackWG), 0, s, cells, ncells,
+                     reinterpret_cast<uint4*>(list), cap, wgcnt, cnt);
+  return hipGetLastError();
+}
+hipError_t launch_cells_pack(hipStream_t s, const uint32_t* cells, uint64_t ncells, void* list, uint64_t cap,
+                             unsigned long long* cnt, uint32_t* wgcnt) {
+  return cells_pack(s, cells, ncells, list, cap, cnt, wgcnt);
+}
+hipError_t launch_cells_pack(hipStream_t s, const uint64_t* cells, uint64_t ncells, void* list, uint64_t cap,
+                             unsigned long long* cnt, uint32_t* wgcnt) {
+  return cells_pack(s, cells, ncells, list, cap, cnt, wgcnt);
+}
+
+template <class CELL>
+static hipError_t cells_add(hipStream_t s, CELL* cells, uint64_t ncells, const void* list, uint64_t n,
+                            unsigned long long* bad) {
+  if (!n) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(cells_add_kernel<CELL>, dim3(grid), dim3(256), 0, s, cells, ncells,
+                     reinterpret_cast<const uint4*>(list), n, bad);
+  return hipGetLastError();
+}
+hipError_t launch_cells_add(hipStream_t s, uint32_t* cells, uint64_t ncells, const void* list, uint64_t n,
+                            unsigned long long* bad) {
+  return cells_add(s, cells, ncells, list, n, bad);
+}
+hipError_t launch_cells_add(hipStream_t s, uint64_t* cells, uint64_t ncells, const void* list, uint64_t n,
+                            unsigned long long* bad) {
+  return cells_add(s, cells, ncells, list, n, bad);
 }
 
 hipError_t launch_merge(hipStream_t s, void* dst, const void* src, uint64_t n, int op) {

@@ -380,6 +380,20 @@ extern "C" int nmg_get_cost_cells(nmg_engine* h, uint64_t* rows, int64_t n) {
   return rows_get(h, h->cost.rows, cost_prepare, rows, n, cost_fill);
 }
 
+// The timeline sparse table's used slots as (key, count) words on the host,
+// sorted by key; none without such a table (the getters' rows and the merge's export)
+static int timeline_sparse_fetch(nmg_engine* h, std::vector<uint64_t>& kv) {
+  Timeline& t = h->tl;
+  kv.clear();
+  if (!t.on || !t.sp_cap) return NMG_OK;
+  HIP_TRY(h, t.d_sp_ck.reserve(t.sp_cap));
+  HIP_TRY(h, t.d_sp_ck.compact(h->stream, t.d_sp_keys.get(), t.d_sp_vals.get()));
+  const int rc = t.d_sp_ck.download(h, kv);
+  if (rc) return rc;
+  sparse_words_sort(kv);
+  return NMG_OK;
+}
+
 // ---- access timeline rows: counted per segment, scanned and emitted on the
 // device (the page cells' pattern)
 int timeline_prepare(nmg_engine* h) {
@@ -408,14 +422,8 @@ int timeline_prepare(nmg_engine* h) {
   // NMG_TL_SCOPE_ALL: the timeline sparse table's used slots, compacted on the
   // device so that only they cross PCIe, sorted by key -- (entry, bin, thread,
   // row) order -- and kept for timeline_fill
-  t.sp_kv.clear();
-  if (t.sp_cap) {
-    HIP_TRY(h, t.d_sp_ck.reserve(t.sp_cap));
-    HIP_TRY(h, t.d_sp_ck.compact(h->stream, t.d_sp_keys.get(), t.d_sp_vals.get()));
-    rc = t.d_sp_ck.download(h, t.sp_kv);
-    if (rc) return rc;
-    sparse_words_sort(t.sp_kv);
-  }
+  rc = timeline_sparse_fetch(h, t.sp_kv);
+  if (rc) return rc;
   t.rows.n = t.nd + (int64_t)(t.sp_kv.size() / 2);
   return NMG_OK;
 }
@@ -450,6 +458,8 @@ extern "C" uint64_t nmg_array_size(nmg_engine* h, int which) {
     case NMG_ARR_MIN64: return h->cnt.n_min64;
     case NMG_ARR_MAX64: return h->cnt.n_max64;
     case NMG_ARR_HIST32: return h->tab.cells() * h->T;
+    case NMG_ARR_COST64: return h->cost.on ? h->tab.cells() * h->T : 0;
+    case NMG_ARR_TL32: return h->tl.on ? h->tl.ncells : 0;
     default: return 0;
   }
 }
@@ -460,6 +470,8 @@ void* array_ptr(nmg_engine* h, int which, size_t* bytes) {
     case NMG_ARR_MIN64: *bytes = h->cnt.n_min64 * 8; return h->cnt.d_min64;
     case NMG_ARR_MAX64: *bytes = h->cnt.n_max64 * 8; return h->cnt.d_max64;
     case NMG_ARR_HIST32: *bytes = h->tab.cells() * h->T * 4; return h->cnt.d_hist;
+    case NMG_ARR_COST64: *bytes = h->cost.on ? h->tab.cells() * h->T * 8 : 0; return h->cost.d_cells;
+    case NMG_ARR_TL32: *bytes = h->tl.on ? h->tl.ncells * 4 : 0; return h->tl.d_cells;
     default: *bytes = 0; return nullptr;
   }
 }
@@ -536,6 +548,52 @@ extern "C" int nmg_hist_unpack(nmg_engine* h, const void* d_u8, const void* d_ov
   HIP_TRY(h, hipMemcpyAsync(&bad, h->d_scratch + 1, 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (bad) return fail(h, NMG_ERR_RANGE, "nmg_hist_unpack: overflow entries outside the histogram");
+  return NMG_OK;
+}
+
+// ---- packed cells: the page cost array (u64) or the timeline array (u32) as a
+// list of its non-zero cells
+static bool cells_array(int which) { return which == NMG_ARR_COST64 || which == NMG_ARR_TL32; }
+
+extern "C" int nmg_cells_pack(nmg_engine* h, int which, void* d_list, uint64_t cap, uint64_t* n) {
+  Range range("nmg_cells_pack");
+  if (!h || !h->have_table || !n || !cells_array(which)) return NMG_ERR_INVALID;
+  *n = 0;
+  const uint64_t cells = nmg_array_size(h, which);
+  if (!cells) return NMG_OK;
+  if (cap && !d_list) return NMG_ERR_INVALID;
+  int rc = scratch_u64(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemsetAsync(h->d_scratch, 0, 8, h->stream));
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(h->d_scratch.get());
+  uint32_t* wgcnt = reinterpret_cast<uint32_t*>(h->d_scratch + 2);
+  if (which == NMG_ARR_COST64) HIP_TRY(h, launch_cells_pack(h->stream, h->cost.d_cells.get(), cells, d_list, cap, cnt, wgcnt));
+  else HIP_TRY(h, launch_cells_pack(h->stream, h->tl.d_cells.get(), cells, d_list, cap, cnt, wgcnt));
+  HIP_TRY(h, hipMemcpyAsync(n, h->d_scratch, 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return NMG_OK;
+}
+
+extern "C" int nmg_cells_unpack_add(nmg_engine* h, int which, const void* d_list, uint64_t n) {
+  if (h) h->epoch++;
+  if (h) h->counters_fresh = false;
+  Range range("nmg_cells_unpack_add");
+  if (!h || !h->have_table || !cells_array(which)) return NMG_ERR_INVALID;
+  const uint64_t cells = nmg_array_size(h, which);
+  if (!cells || !n) return NMG_OK;
+  if (!d_list) return NMG_ERR_INVALID;
+  int rc = scratch_u64(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemsetAsync(h->d_scratch + 1, 0, 8, h->stream));
+  unsigned long long* bad_w = reinterpret_cast<unsigned long long*>(h->d_scratch + 1);
+  if (which == NMG_ARR_COST64) HIP_TRY(h, launch_cells_add(h->stream, h->cost.d_cells.get(), cells, d_list, n, bad_w));
+  else HIP_TRY(h, launch_cells_add(h->stream, h->tl.d_cells.get(), cells, d_list, n, bad_w));
+  uint64_t bad = 0;
+  HIP_TRY(h, hipMemcpyAsync(&bad, h->d_scratch + 1, 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (bad) return fail(h, NMG_ERR_RANGE, "nmg_cells_unpack_add: pairs outside the array");
   return NMG_OK;
 }
 
@@ -632,7 +690,7 @@ int sparse_import_words(nmg_engine* h, const uint64_t* kv, uint64_t n) {
   HIP_TRY(h, sw.reserve(h->sparse_cap));
   HIP_TRY(h, hipMemsetAsync(h->cnt.d_sparse_keys, 0xff, h->sparse_cap * 8, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->cnt.d_sparse_vals, 0, h->sparse_cap * 4, h->stream));
-  // (the slots move: the sparse cost cells start again -- cost cells are not merged across ranks)
+  // (the slots move: the sparse cost cells start again -- the merge follows with nmg_sparse_import_ex(NMG_SPARSE_PAGE_COST))
   if (h->cost.d_sparse) HIP_TRY(h, hipMemsetAsync(h->cost.d_sparse, 0, h->sparse_cap * 8, h->stream));
   if (n) {
     HIP_TRY(h, hipMemcpyAsync(sw.words(), kv, 2 * n * 8, hipMemcpyHostToDevice, h->stream));
@@ -650,6 +708,130 @@ extern "C" int nmg_sparse_import(nmg_engine* h, const uint64_t* keys, const uint
   std::vector<uint64_t> kv;  // (the import refuses the other n without reading a word)
   if (h->cnt.d_sparse_keys && (uint64_t)n <= h->sparse_cap)
     for (int64_t i = 0; i < n; i++) kv.insert(kv.end(), {keys[i], (uint64_t)counts[i]});
+  return sparse_import_words(h, kv.data(), (uint64_t)n);
+}
+
+// ---- the sparse parts by kind (nmg_sparse_*_ex): the page counts, the sparse
+// cost cells at the page table's keys, the timeline sparse table
+
+// kind `which` as (key, value) words sorted by key: the used slots with a
+// non-zero value, through the getters' compaction (SparseWords::compact)
+static int sparse_words_ex(nmg_engine* h, uint32_t which, std::vector<uint64_t>& kv) {
+  kv.clear();
+  int rc = nmg_synchronize(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  switch (which) {
+    case NMG_SPARSE_PAGE_COUNTS: rc = sparse_fetch(h, h->cnt.d_sparse_vals.get(), kv); break;
+    case NMG_SPARSE_PAGE_COST:
+      if (h->cost.on && h->cost.d_sparse) rc = sparse_fetch(h, h->cost.d_sparse.get(), kv);
+      break;
+    case NMG_SPARSE_TIMELINE: return timeline_sparse_fetch(h, kv);  // (sorted there)
+    default: return fail(h, NMG_ERR_INVALID, "nmg_sparse_*_ex: which is NMG_SPARSE_PAGE_COUNTS, _PAGE_COST or _TIMELINE");
+  }
+  if (!rc) sparse_words_sort(kv);
+  return rc;
+}
+
+extern "C" int64_t nmg_sparse_count_ex(nmg_engine* h, uint32_t which) {
+  if (!h || !h->have_table) return NMG_ERR_INVALID;
+  std::vector<uint64_t> kv;
+  const int rc = sparse_words_ex(h, which, kv);
+  return rc ? rc : (int64_t)(kv.size() / 2);
+}
+
+extern "C" int nmg_sparse_export_ex(nmg_engine* h, uint32_t which, uint64_t* keys, uint64_t* vals, int64_t n) {
+  if (!h || !h->have_table || n < 0 || (n && (!keys || !vals))) return NMG_ERR_INVALID;
+  std::vector<uint64_t> kv;
+  const int rc = sparse_words_ex(h, which, kv);
+  if (rc) return rc;
+  if ((int64_t)(kv.size() / 2) != n) return fail(h, NMG_ERR_INVALID, "sparse count mismatch");
+  for (int64_t i = 0; i < n; i++) {
+    keys[i] = kv[2 * i];
+    vals[i] = kv[2 * i + 1];
+  }
+  return NMG_OK;
+}
+
+// n interleaved (key, value) words to the staging sw on the device (enqueued; kv pageable: the caller waits)
+static int stage_words(nmg_engine* h, SparseWords& sw, uint64_t slots, const std::vector<uint64_t>& kv) {
+  HIP_TRY(h, sw.reserve(slots));
+  if (!kv.empty()) HIP_TRY(h, hipMemcpyAsync(sw.words(), kv.data(), kv.size() * 8, hipMemcpyHostToDevice, h->stream));
+  return NMG_OK;
+}
+
+// NMG_SPARSE_PAGE_COST: every sparse cost cell zeroed, then each key's cost stored at its slot of the page table
+static int sparse_cost_import(nmg_engine* h, const std::vector<uint64_t>& kv) {
+  PageCost& c = h->cost;
+  const uint64_t n = kv.size() / 2;
+  if (!c.on || !c.d_sparse || !h->cnt.d_sparse_keys)
+    return n ? fail(h, NMG_ERR_STATE, "nmg_sparse_import_ex: no sparse cost cells (nmg_set_page_cost_ex with "
+                                      "NMG_COST_SCOPE_ALL on an engine with a sparse page table)")
+             : NMG_OK;
+  int rc = nmg_synchronize(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemsetAsync(c.d_sparse, 0, h->sparse_cap * 8, h->stream));
+  uint64_t bad = n > h->sparse_cap ? n - h->sparse_cap : 0;  // (unique keys past the slots: absent, whatever they are)
+  if (n && !bad) {
+    rc = scratch_u64(h);
+    if (!rc) rc = stage_words(h, h->cnt.d_sparse_ck, h->sparse_cap, kv);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->d_scratch + 1, 0, 8, h->stream));
+    HIP_TRY(h, launch_sparse_cost_store(h->stream, h->cnt.d_sparse_keys, c.d_sparse, h->sparse_cap,
+                                        h->cnt.d_sparse_ck.words(), n,
+                                        reinterpret_cast<unsigned long long*>(h->d_scratch + 1)));
+    HIP_TRY(h, hipMemcpyAsync(&bad, h->d_scratch + 1, 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (bad) {
+    HIP_TRY(h, hipMemset(c.d_sparse, 0, h->sparse_cap * 8));
+    char msg[160];
+    snprintf(msg, sizeof(msg), "nmg_sparse_import_ex: %llu cost keys absent from the sparse page table "
+                               "(import the page counts first)", (unsigned long long)bad);
+    return fail(h, NMG_ERR_INVALID, msg);
+  }
+  return NMG_OK;
+}
+
+// NMG_SPARSE_TIMELINE: the timeline sparse table cleared, then the pairs inserted with its own hash
+static int timeline_sparse_import(nmg_engine* h, const std::vector<uint64_t>& kv) {
+  Timeline& t = h->tl;
+  const uint64_t n = kv.size() / 2;
+  if (!t.on || !t.sp_cap)
+    return n ? fail(h, NMG_ERR_STATE, "nmg_sparse_import_ex: no timeline sparse table (nmg_set_timeline_ex with "
+                                      "NMG_TL_SCOPE_ALL and a sparse entry selected)")
+             : NMG_OK;
+  if (n > t.sp_cap) return fail(h, NMG_ERR_CAPACITY, "timeline sparse table too small");
+  for (uint64_t i = 0; i < n; i++)
+    if (kv[2 * i + 1] >> 32) return fail(h, NMG_ERR_RANGE, "nmg_sparse_import_ex: a timeline count of 2^32 or more");
+  int rc = nmg_synchronize(h);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemsetAsync(t.d_sp_keys, 0xff, t.sp_cap * 8, h->stream));
+  HIP_TRY(h, hipMemsetAsync(t.d_sp_vals, 0, t.sp_cap * 4, h->stream));
+  rc = stage_words(h, t.d_sp_ck, t.sp_cap, kv);
+  if (rc) return rc;
+  HIP_TRY(h, launch_tl_sparse_insert(h->stream, t.d_sp_keys, t.d_sp_vals, t.sp_cap, t.d_sp_ck.words(), n));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  t.sp_touched = true;  // imported cells: the next reset must clear the table
+  return NMG_OK;
+}
+
+extern "C" int nmg_sparse_import_ex(nmg_engine* h, uint32_t which, const uint64_t* keys, const uint64_t* vals,
+                                    int64_t n) {
+  if (h) h->epoch++;
+  if (!h || !h->have_table || n < 0 || (n && (!keys || !vals))) return NMG_ERR_INVALID;
+  if (which > NMG_SPARSE_TIMELINE)
+    return fail(h, NMG_ERR_INVALID, "nmg_sparse_import_ex: which is NMG_SPARSE_PAGE_COUNTS, _PAGE_COST or _TIMELINE");
+  std::vector<uint64_t> kv;
+  kv.reserve(2 * (size_t)n);
+  for (int64_t i = 0; i < n; i++) kv.insert(kv.end(), {keys[i], vals[i]});
+  if (which == NMG_SPARSE_PAGE_COST) return sparse_cost_import(h, kv);
+  if (which == NMG_SPARSE_TIMELINE) return timeline_sparse_import(h, kv);
+  if (h->cnt.d_sparse_keys && (uint64_t)n <= h->sparse_cap)  // (sparse_import_words refuses the other n)
+    for (int64_t i = 0; i < n; i++)
+      if (vals[i] >> 32) return fail(h, NMG_ERR_RANGE, "nmg_sparse_import_ex: a page count of 2^32 or more");
   return sparse_import_words(h, kv.data(), (uint64_t)n);
 }
 

@@ -16,7 +16,12 @@ The only exchange step is the merge of the counters:
   (packed, merge_hist_packed: bytes of the cells <= 255 / world summed as
   u8, the larger cells gathered as (cell, count) lists -- 98 -> ~26 MB per
   rank at 1M intervals)
+* u64 page cost cells, u32 timeline cells (when set)                    -> SUM
+  (packed, CellPacker: both arrays are almost all zeros, so each rank's
+  non-zero cells travel as (cell, value) pairs and the root adds them)
 * sparse page cells, per-buffer counts: variable length -> gathered to the root
+* sparse cost cells, the timeline sparse table (when set): (key, value) pairs
+  gathered, summed by key and imported after the sparse page cells
 
 RCCL reduces int64, not uint64: sums are bit-identical under two's
 complement; MIN/MAX use the order-preserving map x ^ 2^63.
@@ -238,12 +243,158 @@ def merge_sparse(parts) -> Tuple[np.ndarray, np.ndarray]:
     return u, (s & 0xFFFFFFFF).astype(np.uint32)
 
 
+def merge_sparse_u64(parts) -> Tuple[np.ndarray, np.ndarray]:
+    """merge_sparse with the sums kept as u64 (cost sums pass 2^32): (keys,
+    values) summed by key, keys ascending and unique."""
+    keys = np.concatenate([np.asarray(p[0], dtype=np.uint64) for p in parts]) if parts else np.zeros(0, np.uint64)
+    vals = np.concatenate([np.asarray(p[1], dtype=np.uint64) for p in parts]) if parts else np.zeros(0, np.uint64)
+    if keys.shape[0] == 0:
+        return keys, vals
+    u, inv = np.unique(keys, return_inverse=True)
+    s = np.zeros(u.shape[0], dtype=np.uint64)
+    np.add.at(s, inv.reshape(-1), vals)
+    return u, s
+
+
+_TIMELINE_FIELDS = ("t0", "bin_shift", "nb_bins", "row_shift", "min_object_bytes", "budget_bytes", "scope")
+_PAGE_COST_FIELDS = ("bucket_mask", "access_mask", "metric", "budget_bytes", "scope")
+
+
+def options_digest(timeline_opts: Optional[dict], page_cost_opts: Optional[dict]) -> int:
+    """A 62-bit digest of the product options an engine remembers
+    (Engine.timeline_opts, Engine.page_cost_opts; None: not set): equal options
+    give equal digests on every rank, a difference in any field, the scope
+    included, another one.  Non-negative, so it travels as int64."""
+    import hashlib
+
+    def words(o, fields):
+        return (0,) if o is None else (1,) + tuple(int(o[f]) for f in fields)
+
+    text = repr((words(timeline_opts, _TIMELINE_FIELDS), words(page_cost_opts, _PAGE_COST_FIELDS)))
+    return int.from_bytes(hashlib.blake2b(text.encode(), digest_size=8).digest(), "little") >> 2
+
+
+def check_products(eng, group=None, device=None) -> Tuple[int, int]:
+    """Every rank's page cost and timeline arrays must have one size and one
+    set of options before they meet in a collective: (NMG_ARR_COST64 size,
+    NMG_ARR_TL32 size), or RuntimeError on every rank when some rank differs (a
+    rank that forgot set_page_cost would otherwise hang the job in a reduce the
+    others never enter, or add cells counted by another rule)."""
+    import torch
+    import torch.distributed as dist
+
+    from . import _lib
+
+    mine = [eng.array_size(_lib.NMG_ARR_COST64), eng.array_size(_lib.NMG_ARR_TL32),
+            options_digest(getattr(eng, "timeline_opts", None), getattr(eng, "page_cost_opts", None))]
+    on_dev = dist.get_backend(group) == "nccl"
+    lo = torch.tensor(mine, dtype=torch.int64, device=device if on_dev else "cpu")
+    hi = lo.clone()
+    dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+    if not torch.equal(lo, hi):
+        what = [name for name, a, b in zip(("page cost cells", "timeline cells", "product options"), lo.tolist(),
+                                           hi.tolist()) if a != b]
+        raise RuntimeError(f"merge_engine: the ranks differ in {', '.join(what)} (this rank: {mine[0]} cost cells, "
+                           f"{mine[1]} timeline cells): give every rank the same table, nb_threads, "
+                           "hist_budget_bytes, set_timeline and set_page_cost")
+    return mine[0], mine[1]
+
+
+class CellPacker:
+    """Buffers of the packed merge of one engine's page cost cells
+    (NMG_ARR_COST64) or timeline cells (NMG_ARR_TL32): the non-zero cells as
+    (cell index, value) pairs (nmg_cells_pack), gathered and added on the root
+    (nmg_cells_unpack_add).  Allocated once; the list holds up to `frac` of
+    the cells, or `cap` pairs -- a buffer size only: a longer list falls back
+    to the dense reduce."""
+
+    def __init__(self, eng, device, which: int, frac: float = 0.125, cap: Optional[int] = None):
+        import torch
+
+        from . import _lib
+
+        assert which in (_lib.NMG_ARR_COST64, _lib.NMG_ARR_TL32)
+        self.eng = eng
+        self.which = which
+        self.cells = eng.array_size(which)
+        self.cap = int(cap) if cap is not None else max(1024, int(self.cells * frac))
+        # (empty: nmg_cells_pack writes pairs [0, n) on the engine's stream; merge() zeroes the padding)
+        self.list = torch.empty(2 * max(self.cap, 1), dtype=torch.int64, device=device)
+        self.n = torch.zeros(1, dtype=torch.int64, device=device)
+        self.dense = None  # fallback: the array itself (a list longer than cap)
+        self.last = (0, 0)  # (packed list bytes, dense array bytes) of the last merge
+
+    def merge_dense(self, dst: int = 0, group=None) -> int:
+        """The array itself reduced into rank dst's engine; returns its bytes."""
+        import torch
+        import torch.distributed as dist
+
+        from . import _lib
+
+        if not self.cells:
+            return 0
+        u64 = self.which == _lib.NMG_ARR_COST64
+        if self.dense is None:
+            self.dense = torch.empty(self.cells, dtype=torch.int64 if u64 else torch.int32, device=self.list.device)
+        self.eng.export_array(self.which, self.dense.data_ptr())
+        if u64:
+            reduce_u64(self.dense, "sum", dst=dst, group=group)
+        else:
+            reduce_u32_sum(self.dense, dst=dst, group=group)
+        if dist.get_rank(group) == dst:
+            torch.cuda.synchronize(self.list.device)
+            self.eng.import_array(self.which, self.dense.data_ptr())
+        return self.cells * (8 if u64 else 4)
+
+    def merge(self, dst: int = 0, group=None) -> int:
+        """Merge every rank's cells into rank dst's engine; returns the bytes
+        this rank contributed to the collectives."""
+        import torch
+        import torch.distributed as dist
+
+        from . import _lib
+
+        if not self.cells:
+            return 0
+        world = dist.get_world_size(group)
+        rank = dist.get_rank(group)
+        dense_bytes = self.cells * (8 if self.which == _lib.NMG_ARR_COST64 else 4)
+        n = self.eng.cells_pack(self.which, self.list.data_ptr(), self.cap)
+        self.n.fill_(n)
+        _collective(self.n, dist.ReduceOp.MAX, None, group)  # every rank: the longest list
+        nmax = int(self.n.item())
+        self.last = (n * 16, dense_bytes)
+        if nmax > self.cap:  # some list does not fit: the array itself
+            return self.merge_dense(dst=dst, group=group)
+        if n < nmax:
+            self.list[2 * n:2 * nmax].zero_()  # (padding: value 0)
+        part = self.list[:2 * nmax]
+        if dist.get_backend(group) == "nccl":
+            out = [torch.empty_like(part) for _ in range(world)] if rank == dst else None
+            dist.gather(part, out, dst=dst, group=group)
+        else:  # (gloo test runs: host staging)
+            cpu = part.cpu()
+            out = [torch.empty_like(cpu) for _ in range(world)] if rank == dst else None
+            dist.gather(cpu, out, dst=dst, group=group)
+        if rank == dst and nmax and world > 1:
+            # the other ranks' lists: this rank's cells are in place already
+            others = torch.cat([o.to(self.list.device) for r, o in enumerate(out) if r != dst])
+            torch.cuda.synchronize(self.list.device)
+            self.eng.cells_unpack_add(self.which, others.data_ptr(), others.numel() // 2)
+        return nmax * 16
+
+
 def merge_engine(eng, dst: int = 0, group=None, device=None, packed_hist: bool = False) -> int:
     """Merge every rank's partial counters into rank dst's engine (RCCL reduce
     of the dense arrays over xGMI; gathers of the small variable-length ones).
-    packed_hist: the page histogram through HistPacker (bytes + overflow)
-    and the per-object counters through ObjPacker (u32 words + overflow).
-    Returns the bytes this rank contributed to the dense collectives."""
+    packed_hist: the page histogram through HistPacker (bytes + overflow),
+    the per-object counters through ObjPacker (u32 words + overflow), and the
+    page cost and timeline cells through CellPacker (their non-zero cells).
+    The page cost cells and the timeline, dense and sparse, are merged when
+    set -- on every rank with the same options, or RuntimeError on every rank
+    (check_products).  Returns the bytes this rank contributed to the dense
+    collectives and to the gathers of the cost and timeline cells."""
     import torch
     import torch.distributed as dist
 
@@ -251,6 +402,7 @@ def merge_engine(eng, dst: int = 0, group=None, device=None, packed_hist: bool =
 
     rank = dist.get_rank(group)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    n_cost, n_tl = check_products(eng, group=group, device=dev)  # (before anything is merged)
     nbytes = 0
     for which, op in ((_lib.NMG_ARR_SUM64, "sum"), (_lib.NMG_ARR_MIN64, "min"), (_lib.NMG_ARR_MAX64, "max")):
         n = eng.array_size(which)
@@ -290,23 +442,42 @@ def merge_engine(eng, dst: int = 0, group=None, device=None, packed_hist: bool =
         if rank == dst:
             torch.cuda.synchronize(dev)
             eng.import_array(_lib.NMG_ARR_HIST32, t.data_ptr())
-    merge_host_side(eng, dst=dst, group=group)
+    # the page cost cells and the timeline cells: mostly zeros, so their non-zero cells (packed_hist) or the arrays
+    packers = eng.__dict__.setdefault("_cell_packers", {})  # one per array and engine, reused across merges
+    for which, n in ((_lib.NMG_ARR_COST64, n_cost), (_lib.NMG_ARR_TL32, n_tl)):
+        if not n:
+            continue
+        cp = packers.get(which)
+        if cp is None or cp.cells != n:
+            cp = packers[which] = CellPacker(eng, dev, which)
+        nbytes += cp.merge(dst=dst, group=group) if packed_hist else cp.merge_dense(dst=dst, group=group)
+    kinds = [k for k, on in ((_lib.NMG_SPARSE_PAGE_COST, eng.page_cost_opts is not None),
+                             (_lib.NMG_SPARSE_TIMELINE, eng.timeline_opts is not None)) if on]
+    nbytes += merge_host_side(eng, dst=dst, group=group, kinds=kinds)
     return nbytes
 
 
-def merge_host_side(eng, dst: int = 0, group=None) -> None:
-    """Sparse page cells and per-buffer counts (variable length): gathered."""
+def merge_host_side(eng, dst: int = 0, group=None, kinds: Sequence[int] = ()) -> int:
+    """Sparse page cells and per-buffer counts (variable length): gathered.
+    kinds: the further sparse kinds to merge (NMG_SPARSE_PAGE_COST,
+    NMG_SPARSE_TIMELINE; the same on every rank), exported before the root's
+    page table is rebuilt and imported after it; returns their bytes."""
     import torch.distributed as dist
 
     rank = dist.get_rank(group)
     k, v = eng.sparse_export()
+    extra = [np.stack(eng.sparse_export_ex(kind)) for kind in kinds]
     parts = gather_arrays(np.stack([k, v.astype(np.uint64)]) if k.shape[0] else np.zeros((2, 0), np.uint64),
                           dst=dst, group=group)
     s, f = eng.buffer_counts()
     nbytes = np.asarray(eng.buffer_bytes, dtype=np.uint64)
     counts = gather_arrays(np.stack([s.astype(np.uint64), f.astype(np.uint64), nbytes]), dst=dst, group=group)
+    extras = gather_arrays(extra, dst=dst, group=group) if kinds else None
     if rank == dst:
         keys, vals = merge_sparse([(p[0], p[1].astype(np.uint32)) for p in parts])
-        eng.sparse_import(keys, vals)
+        eng.sparse_import(keys, vals)  # (zeroes the sparse cost cells: the cost import follows)
         allc = np.concatenate(counts, axis=1)
         eng.set_buffer_counts(allc[0].astype(np.uint32), allc[1].astype(np.uint32), allc[2])
+        for i, kind in enumerate(kinds):
+            eng.sparse_import_ex(kind, *merge_sparse_u64([(p[i][0], p[i][1]) for p in extras]))
+    return sum(16 * int(e.shape[1]) for e in extra)

@@ -58,6 +58,10 @@ class Engine:
         self.table: Optional[ObjectTable] = None
         self.nb_entries = 0
         self.buffer_bytes: list = []  # lengths of the analysed (non-empty) buffers
+        # the options last given to set_timeline / set_page_cost, scope included (None: none set, or
+        # dropped): what distributed.merge_engine compares across the ranks
+        self.timeline_opts: Optional[dict] = None
+        self.page_cost_opts: Optional[dict] = None
 
     def close(self):
         if self.h:
@@ -82,6 +86,7 @@ class Engine:
                                     objs.ctypes.data_as(C.POINTER(_lib.nmg_object)), table.nb_entries))
         self.table = table
         self.nb_entries = table.nb_entries  # (the engine's entry count: update_objects may add ids)
+        self.timeline_opts = self.page_cost_opts = None  # (nmg_set_objects drops both products)
 
     def update_objects(self, keys: np.ndarray, entry_off: np.ndarray, entry_ids: np.ndarray, objs: np.ndarray):
         """nmg_update_objects: the table at an alarm (--online-analysis); objs in
@@ -350,6 +355,9 @@ class Engine:
             self._c(lib.nmg_set_timeline_ex(self.h, o, scope))
         else:
             self._c(lib.nmg_set_timeline(self.h, o))
+        self.timeline_opts = None if t0 is None else dict(
+            t0=t0, bin_shift=bin_shift, nb_bins=nb_bins, row_shift=row_shift, min_object_bytes=min_object_bytes,
+            budget_bytes=budget_bytes, scope=scope)
 
     def timeline_cells(self) -> np.ndarray:
         """The non-zero timeline cells as (entry, bin, thread, row, count) rows,
@@ -380,6 +388,8 @@ class Engine:
             self._c(lib.nmg_set_page_cost_ex(self.h, o, scope))
         else:
             self._c(lib.nmg_set_page_cost(self.h, o))
+        self.page_cost_opts = None if bucket_mask is None else dict(
+            bucket_mask=bucket_mask, access_mask=access_mask, metric=metric, budget_bytes=budget_bytes, scope=scope)
 
     def cost_cells(self) -> np.ndarray:
         """The non-zero cost cells as u64 (entry, thread, page, value) rows,
@@ -451,6 +461,37 @@ class Engine:
 
     def objcw_unpack(self, d_sum64: int, d_u32: int, d_ovf: int, n_ovf: int):
         self._c(lib.nmg_objcw_unpack(self.h, C.c_void_p(d_sum64), C.c_void_p(d_u32), C.c_void_p(d_ovf), n_ovf))
+
+    def cells_pack(self, which: int, d_list: int, cap: int) -> int:
+        """nmg_cells_pack: the non-zero cells of NMG_ARR_COST64 / NMG_ARR_TL32 as
+        (cell index, value) u64 pairs in cell order into d_list (device, cap
+        pairs); returns their number (> cap: the list is incomplete)."""
+        n = C.c_uint64(0)
+        self._c(lib.nmg_cells_pack(self.h, which, C.c_void_p(d_list), cap, C.byref(n)))
+        return n.value
+
+    def cells_unpack_add(self, which: int, d_list: int, n: int):
+        """nmg_cells_unpack_add: array[index] += value for n (index, value) pairs on the device."""
+        self._c(lib.nmg_cells_unpack_add(self.h, which, C.c_void_p(d_list), n))
+
+    def sparse_export_ex(self, which: int):
+        """nmg_sparse_export_ex: (keys, u64 values) of one sparse kind
+        (NMG_SPARSE_*), ascending unique keys, non-zero values."""
+        n = lib.nmg_sparse_count_ex(self.h, which)
+        self._c(n)
+        k = np.zeros(n, dtype=np.uint64)
+        v = np.zeros(n, dtype=np.uint64)
+        self._c(lib.nmg_sparse_export_ex(self.h, which, _ptr(k, C.c_uint64), _ptr(v, C.c_uint64), n))
+        return k, v
+
+    def sparse_import_ex(self, which: int, keys: np.ndarray, vals: np.ndarray):
+        """nmg_sparse_import_ex: replace one sparse kind's cells (the cost
+        cells after sparse_import: their keys must be in the page table)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        if keys.shape != vals.shape:
+            raise ValueError("sparse_import_ex: keys and vals differ in length")
+        self._c(lib.nmg_sparse_import_ex(self.h, which, _ptr(keys, C.c_uint64), _ptr(vals, C.c_uint64), keys.shape[0]))
 
     def sparse_export(self):
         n = lib.nmg_sparse_count(self.h)
