@@ -1211,6 +1211,29 @@ int64_t nmo_lookup(const uint64_t *keys, const uint32_t *entry_off, uint32_t nb_
   return -1;
 }
 
+/* o_update_counters on caller-provided samples (tests pin this against the
+ * reference's own update_counters in oracle/_ref/libref_loop.so).  fresh != 0:
+ * both counters are initialised before every sample and written to out[i]
+ * (2 * 600 bytes each); fresh == 0: initialised once, they take all n
+ * samples, and out holds the one pair. */
+int nmo_update_counters(int64_t n, const uint64_t *data_src, const uint64_t *weight, int access, int fresh,
+                        uint8_t *out) {
+  struct o_counters c[2];
+  if (access < 0 || access >= ACCESS_MAX) return NMO_ERR_FORMAT;
+  o_init_counters(&c[0]);
+  o_init_counters(&c[1]);
+  for (int64_t i = 0; i < n; i++) {
+    if (fresh) {
+      o_init_counters(&c[0]);
+      o_init_counters(&c[1]);
+    }
+    o_update_counters(c, weight[i], data_src[i], access);
+    if (fresh) memcpy(out + (size_t)i * sizeof(c), c, sizeof(c));
+  }
+  if (!fresh) memcpy(out, c, sizeof(c));
+  return 0;
+}
+
 const char *nmo_strerror(int rc) {
   switch (rc) {
     case 0: return "ok";

@@ -67,5 +67,7 @@ int nmo_run(const char *replay_path, const char *outdir, const char *stdout_path
 const char *nmo_strerror(int rc);
 int64_t nmo_lookup(const uint64_t *keys, const uint32_t *entry_off, uint32_t nb_keys,
                    const uint64_t *ent4, uint64_t addr, uint64_t ts);
+int nmo_update_counters(int64_t n, const uint64_t *data_src, const uint64_t *weight, int access, int fresh,
+                        uint8_t *out);
 
 #endif

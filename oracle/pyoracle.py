@@ -1,5 +1,6 @@
-"""TEST INFRASTRUCTURE ONLY -- ctypes access to the CPU oracle (liboracle.so)
-and to the reference's own AVL index (oracle/_ref/libref_hash.so).
+"""TEST INFRASTRUCTURE ONLY -- ctypes access to the CPU oracle (liboracle.so),
+to the reference's own AVL index (oracle/_ref/libref_hash.so) and to its own
+sample loop (oracle/_ref/libref_loop.so).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use
 this module, and only as the checker / CPU baseline.
@@ -128,6 +129,185 @@ def ref():
         lib.ref_size.restype = C.c_int
         _ref = lib
     return _ref
+
+
+# ---- the reference's own sample loop (oracle/ref_loop_shim.c -> oracle/_ref/libref_loop.so)
+REF_LOOP_SO = os.path.join(HERE, "_ref", "libref_loop.so")
+RL_OK, RL_ABORT, RL_ASSERT = 0, 1, 2  # ref_loop_shim.c: how a call into the reference ended
+COUNTERS_BYTES = 600  # struct mem_counters (tests/test_abi.py)
+
+_ref_loop = None
+
+
+def ref_loop_available() -> bool:
+    return os.path.exists(REF_LOOP_SO)
+
+
+def ref_loop():
+    """The reference's src/mem_sampling.c + src/mem_analyzer.c (unchanged)
+    behind oracle/ref_loop_shim.c."""
+    global _ref_loop
+    if _ref_loop is None:
+        lib = C.CDLL(REF_LOOP_SO)
+        u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+        lib.rl_reset.argtypes = [C.c_int]
+        lib.rl_add.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+        lib.rl_move.argtypes = [C.c_int, C.c_uint64]
+        lib.rl_free.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
+        lib.rl_object.argtypes = [C.c_int, u64p]
+        lib.rl_find.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rl_feed.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint, C.c_int, i32p]
+        lib.rl_globals.argtypes = [C.c_void_p, u64p]
+        lib.rl_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int64]
+        lib.rl_blocks.restype = C.c_int64
+        lib.rl_update_counters.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        assert lib.rl_counters_bytes() == COUNTERS_BYTES
+        _ref_loop = lib
+    return _ref_loop
+
+
+def _counter_pairs(fn, data_src, weight, access: int, fresh: bool):
+    import numpy as np
+
+    ds = np.ascontiguousarray(data_src, dtype=np.uint64)
+    w = np.ascontiguousarray(weight, dtype=np.uint64)
+    assert ds.shape == w.shape
+    out = np.zeros((ds.shape[0] if fresh else 1, 2 * COUNTERS_BYTES), dtype=np.uint8)
+    rc = fn(ds.shape[0], ds.ctypes.data, w.ctypes.data, access, int(fresh), out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"update_counters failed ({rc})")
+    return out
+
+
+def ref_update_counters(data_src, weight, access: int, fresh: bool = True):
+    """The reference's update_counters on (data_src, weight) samples: the
+    bytes of struct mem_counters[2], per sample on fresh counters (fresh) or
+    once after all of them."""
+    return _counter_pairs(ref_loop().rl_update_counters, data_src, weight, access, fresh)
+
+
+def update_counters(data_src, weight, access: int, fresh: bool = True):
+    """The oracle's o_update_counters, as ref_update_counters."""
+    lib = oracle()
+    lib.nmo_update_counters.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    return _counter_pairs(lib.nmo_update_counters, data_src, weight, access, fresh)
+
+
+class RefLoop:
+    """One run of the reference's loop: objects in, buffers through
+    __copy_buffer + __analyze_buffer, counters out.  The library holds one
+    state: a new RefLoop resets it."""
+
+    def __init__(self, match_samples: bool = True):
+        self.lib = ref_loop()
+        self._ok(self.lib.rl_reset(int(match_samples)))
+        self.buf_samples, self.buf_found, self.status = [], [], []
+
+    @staticmethod
+    def _ok(rc):
+        if rc:
+            raise RuntimeError(f"the reference stopped ({'abort' if rc == RL_ABORT else 'assert' if rc == RL_ASSERT else rc})")
+
+    def add(self, kind: int, addr: int, size: int, alloc_date: int, free_date: int) -> int:
+        idx = self.lib.rl_add(kind, addr, size, alloc_date, free_date)
+        if idx < 0:
+            self._ok(-1 - idx)
+        return idx
+
+    def move(self, idx: int, new_addr: int):
+        self._ok(self.lib.rl_move(idx, new_addr))
+
+    def free(self, idx: int, size: int, free_date: int):
+        self._ok(self.lib.rl_free(idx, size, free_date))
+
+    def object(self, idx: int):
+        out = (C.c_uint64 * 6)()
+        self._ok(self.lib.rl_object(idx, out))
+        return list(out)
+
+    def add_table(self, table):
+        """The objects of a flattened table (numamma_amd.replay.ObjectTable),
+        each key's entries oldest first (the AVL node's list is newest-first),
+        through the calls the traced process would have made: malloc at the
+        key, realloc to buffer_addr where it differs, free with the final
+        size; globals and the [stack] by their own paths.  Returns
+        obj_of_entry (the shim's number per entry)."""
+        import numpy as np
+
+        ent, off = table.entries, table.entry_off.astype(np.int64)
+        obj = np.full(ent.shape[0], -1, dtype=np.int64)
+        for k in range(table.nb_keys):
+            key = int(table.keys[k])
+            for e in range(int(off[k + 1]) - 1, int(off[k]) - 1, -1):
+                x = ent[e]
+                mt, addr, size = int(x["mem_type"]), int(x["buffer_addr"]), int(x["buffer_size"])
+                al, fr = int(x["alloc_date"]), int(x["free_date"])
+                if mt == 2:  # [stack]: the reference's fixed range
+                    i = self.add(2, 0, 0, al, fr)
+                    assert self.object(i)[:2] == [addr, size] and key == addr
+                elif mt == 3:  # dynamic_allocation
+                    i = self.add(0, key, int(x["initial_buffer_size"]), al, 0)
+                    if addr != key:
+                        self.move(i, addr)
+                    self.free(i, size, fr)
+                else:  # global_symbol / lib
+                    assert key == addr
+                    i = self.add(1, addr, size, al, fr)
+                obj[e] = i
+        return obj
+
+    def find(self, addr, ts):
+        """ma_find_mem_info_from_sample per (addr, timestamp): the shim's object number, -1 for none."""
+        import numpy as np
+
+        a = np.ascontiguousarray(addr, dtype=np.uint64)
+        t = np.ascontiguousarray(ts, dtype=np.uint64)
+        out = np.zeros(a.shape[0], dtype=np.int32)
+        self._ok(self.lib.rl_find(a.shape[0], a.ctypes.data, t.ctypes.data, out.ctypes.data))
+        return out
+
+    def feed(self, ring, data_tail: int, data_head: int, thread_rank: int, access: int):
+        """One ring through __copy_buffer and __analyze_buffer.  Returns
+        (status, samples, found); an empty ring (head == tail) is not recorded
+        as a buffer, as it gets no analysis index."""
+        import numpy as np
+
+        ring = np.ascontiguousarray(ring, dtype=np.uint8)
+        if data_head >= ring.shape[0]:
+            # a replay's buffer is a struct sample_list, whose data_head may equal the ring's size; the
+            # mmap page's data_head is reduced modulo data_size (mem_sampling.c:936) and would read as 0:
+            # describe the same bytes as a ring with one unread slot after them
+            ring = np.concatenate([ring, np.zeros(data_head + 8 - ring.shape[0], dtype=np.uint8)])
+        cnt = (C.c_int32 * 2)()
+        st = self.lib.rl_feed(ring.ctypes.data, ring.shape[0], data_tail, data_head, thread_rank, access, cnt)
+        if data_head % ring.shape[0] != data_tail:
+            self.buf_samples.append(cnt[0])
+            self.buf_found.append(cnt[1])
+            self.status.append(st)
+        return st, cnt[0], cnt[1]
+
+    def global_counters(self):
+        """(raw bytes of global_counters[2], samples, found)"""
+        import numpy as np
+
+        out = np.zeros(2 * COUNTERS_BYTES, dtype=np.uint8)
+        tot = (C.c_uint64 * 2)()
+        assert self.lib.rl_globals(out.ctypes.data, tot) == 2 * COUNTERS_BYTES
+        return out, tot[0], tot[1]
+
+    def blocks(self, idx: int):
+        """u64 rows (thread, block id, counters[READ] 75 words, counters[WRITE]
+        75 words) of an object's page blocks with a count; None if it never matched."""
+        import numpy as np
+
+        width = 2 + 2 * COUNTERS_BYTES // 8
+        n = self.lib.rl_blocks(idx, None, 0)
+        if n == -1:
+            return None
+        assert n >= 0
+        out = np.zeros((n, width), dtype=np.uint64)
+        assert self.lib.rl_blocks(idx, out.ctypes.data, n) == n
+        return out
 
 
 # ---- the multi-threaded restatement (oracle/nmg_cpu_mt.cpp)
